@@ -8,20 +8,33 @@ training step: BN buffer broadcast, forward, cross-entropy, top-1 accuracy, metr
 backward with bucketed RCCL gradient all-reduce overlapped with backward, SGD(momentum 0.9, wd 1e-4)
 step.  Compute dtype bf16 (fp32 master weights / gradients / BN statistics).
 
-Single GPU:  python bench.py [--steps K --warmup W]
+Single GPU:  python bench.py [--gpus 1 --steps K --warmup W]
 N GPUs:      python bench.py --gpus N ...       (spawns N ranks itself through our launcher), or
              python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
                  --master-port P bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.  ``vs_baseline`` divides by the reference's best published node
 throughput (DDP, 3x TITAN Xp: 5 x 1,281,167 images / 4612 s = 1389 img/s).
 
+A plain run does only what the headline figure needs: set up, warm up, time ``--steps`` steps, write
+the outputs (``--dump-outputs``) and print the JSON line.  ``--full`` adds the checks and side
+measurements (below); a run without it reports their fields as null.
+
 Collectives (``--comm``): ``native`` (default) = this framework's own RCCL communicator and C++
 gradient bucketer on its own HIP stream (csrc/comm.cpp) for EVERY GPU collective of the step, with
 torch.distributed (gloo) used only as the rendezvous store; ``torch`` = RCCL through c10d
-ProcessGroupNCCL.  After the timed steps the ranks compare fp64 checksums of their parameters
-(``params_equal_across_ranks``: DDP replicas must stay bit-identical) and the JSON records the RCCL
-communicator size, the gradient bucket layout and the exposed (not overlapped) gradient all-reduce
-time per step, measured with HIP events around the bucketer's final wait.
+ProcessGroupNCCL.  With ``--full`` a communicator self-test runs before the steps
+(``comm_selftest``), after the timed steps the ranks compare fp64 checksums of their parameters
+(``params_equal_across_ranks``: DDP replicas must stay bit-identical; exit status 4 if not) and the
+JSON records the exposed (not overlapped) gradient all-reduce time per step, measured with HIP events
+around the bucketer's final wait.  The RCCL communicator size and the gradient bucket layout are
+always recorded.
+
+``--dump-outputs DIR`` writes what the last timed step returned and left behind as ``DIR/<name>.npy``
+(rank r > 0: ``<name>_rank<r>.npy``): ``logits`` (float32) and ``metrics`` (float64), the two tensors
+``train_step`` returns, and ``params`` (float32), the fp32 master parameters after that step's SGD
+update.  Model, inputs and the sample positions are seeded, so two builds run with the same
+arguments can be compared array for array.  An array over its share of the 64 MB budget is
+written as a fixed sample of its elements (flat positions drawn once from a seeded CPU generator).
 """
 import argparse
 import json
@@ -31,6 +44,8 @@ import subprocess
 import sys
 import time
 
+DUMP_MAX_ELEMS = 15_000_000  # --dump-outputs: fp32 elements in all (60 MB), under the 64 MB budget
+DUMP_MAX_LOGITS = 5_000_000  # ... of which the logits take at most this many
 REF_IMG_PER_S = 5 * 1281167 / 4612.0  # BASELINE.md, DDP row (derived from README.md:12)
 ROOT = os.path.dirname(os.path.abspath(__file__))
 
@@ -39,7 +54,7 @@ def _parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); without a launcher environment bench.py spawns them itself")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--arch", default="resnet18")
     ap.add_argument("--batch-per-gpu", type=int, default=1200)
@@ -64,7 +79,39 @@ def _parse():
                     help="native comm transport: rccl (one rank per GPU), host (shared memory; ranks sharing a GPU)")
     ap.add_argument("--grad-compress", default="none", choices=["none", "bf16"],
                     help="native comm: bf16 gradient all-reduce (default none: fp32, the reference's precision)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the communicator self-test, the cross-rank parameter checksum comparison and "
+                         "the exposed-communication read-out (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's logits / metrics and the updated master "
+                         "parameters as DIR/<name>.npy (<= 64 MB in all; larger arrays as a fixed seeded sample)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def _dump_outputs(out_dir, rank, arrays):
+    """``arrays``: (name, tensor, numpy dtype, element cap) in order; each is written whole if it fits its cap and
+    what is left of DUMP_MAX_ELEMS, else as the elements at seeded random flat positions (sorted, fixed per name
+    and size, so every build samples the same ones)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    left = DUMP_MAX_ELEMS
+    for seed, (name, t, np_dtype, cap) in enumerate(arrays):
+        flat = t.detach().reshape(-1)
+        n, k = flat.numel(), min(flat.numel(), cap, left)
+        if k < n:
+            g = torch.Generator()
+            g.manual_seed(4321 + seed)
+            idx = torch.randint(0, n, (k,), generator=g).sort().values
+            a = flat[idx.to(flat.device)].cpu().double().numpy().astype(np_dtype)
+        else:
+            a = flat.cpu().double().numpy().astype(np_dtype).reshape(tuple(t.shape))
+        left -= k
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
 
 
 def _free_port() -> int:
@@ -134,6 +181,7 @@ def main() -> int:
     torch.manual_seed(0)
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
     model = registry.create(args.arch)
+    # time_comm with or without --full: the timed step is the same in both (the events are only read with --full)
     tr = NativeTrainer(model, dev, dtype=dtype, lr=0.1, momentum=0.9, weight_decay=1e-4,
                        use_amp=(args.dtype == "fp16"), sync_bn=args.sync_bn, bucket_cap_mb=args.bucket_cap_mb,
                        graph=args.graph, autotune=args.autotune, comm=comm, force_comm=args.force_comm,
@@ -154,13 +202,15 @@ def main() -> int:
         elif world > 1:
             dist.all_reduce(t, op={"max": dist.ReduceOp.MAX, "sum": dist.ReduceOp.SUM}[op])
 
-    # communicator self-test: a rank-dependent all-reduce must give the closed-form sum on every rank
-    probe = torch.full((1024,), float(rank + 1), dtype=torch.float32, device=dev)
-    all_reduce(probe, "sum")
-    comm_ok = bool(torch.all(probe == world * (world + 1) / 2).item())
-    if not comm_ok:
-        sys.stderr.write(f"bench.py: rank {rank}: communicator self-test FAILED\n")
-        return 3
+    comm_ok = None
+    if args.full:
+        # communicator self-test: a rank-dependent all-reduce must give the closed-form sum on every rank
+        probe = torch.full((1024,), float(rank + 1), dtype=torch.float32, device=dev)
+        all_reduce(probe, "sum")
+        comm_ok = bool(torch.all(probe == world * (world + 1) / 2).item())
+        if not comm_ok:
+            sys.stderr.write(f"bench.py: rank {rank}: communicator self-test FAILED\n")
+            return 3
 
     B = args.batch_per_gpu
     g = torch.Generator(device=dev)
@@ -175,16 +225,17 @@ def main() -> int:
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
-    tr.exposed_comm_ms()  # drop the warm-up samples
+    if args.full:
+        tr.exposed_comm_ms()  # drop the warm-up samples
     if args.autotune and rank == 0:
         for k, v in tr.executor._tiles.items():
             print("tile", k, v, file=sys.stderr)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    met = None
+    logits = met = None
     for i in range(args.steps):
-        _, met = step(i)
+        logits, met = step(i)
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
@@ -192,19 +243,28 @@ def main() -> int:
     el_t = torch.tensor([el], dtype=torch.float64, device=dev)
     all_reduce(el_t, "max")
     el = float(el_t.item())
-    exposed = tr.exposed_comm_ms()
-    exp_t = torch.tensor([exposed or 0.0], dtype=torch.float64, device=dev)
-    all_reduce(exp_t, "max")
-    # DDP invariant: replicas stay bit-identical -- compare every rank's checksum with rank 0's
-    ck = tr.param_checksum()
-    ref = ck.clone()
-    if nc is not None and world > 1:
-        nc.broadcast(ref, 0)
-    elif world > 1:
-        dist.broadcast(ref, 0)
-    mism = torch.tensor([0.0 if torch.equal(ck, ref) else 1.0], dtype=torch.float64, device=dev)
-    all_reduce(mism, "sum")
-    params_equal = bool(mism.item() == 0)
+    exposed_ms = params_equal = None
+    if args.full:
+        exposed = tr.exposed_comm_ms()
+        exp_t = torch.tensor([exposed or 0.0], dtype=torch.float64, device=dev)
+        all_reduce(exp_t, "max")
+        if world > 1 or nc is not None:
+            exposed_ms = round(float(exp_t.item()), 3)
+        # DDP invariant: replicas stay bit-identical -- compare every rank's checksum with rank 0's
+        ck = tr.param_checksum()
+        ref = ck.clone()
+        if nc is not None and world > 1:
+            nc.broadcast(ref, 0)
+        elif world > 1:
+            dist.broadcast(ref, 0)
+        mism = torch.tensor([0.0 if torch.equal(ck, ref) else 1.0], dtype=torch.float64, device=dev)
+        all_reduce(mism, "sum")
+        params_equal = bool(mism.item() == 0)
+    if args.dump_outputs:
+        import numpy as np
+        _dump_outputs(args.dump_outputs, rank, [("logits", logits, np.float32, DUMP_MAX_LOGITS),
+                                                ("metrics", met, np.float64, DUMP_MAX_ELEMS),
+                                                ("params", tr.flat.data, np.float32, DUMP_MAX_ELEMS)])
     ms = el / args.steps * 1e3
     value = world * B * args.steps / el
     if rank == 0:
@@ -227,8 +287,7 @@ def main() -> int:
                        "params_equal_across_ranks": params_equal,
                        "bucket_sizes_mb": [round(x, 3) for x in tr.bucketer.bucket_sizes_mb()] if world > 1 else [],
                        "grad_compress": args.grad_compress if comm == "native" else "none",
-                       "exposed_comm_ms_per_step": round(float(exp_t.item()), 3) if world > 1 or nc is not None
-                       else None,
+                       "exposed_comm_ms_per_step": exposed_ms,
                        "last_loss": round(float(met[0].item()), 4) if met is not None else None}}), flush=True)
     if world > 1:
         barrier()
@@ -236,7 +295,7 @@ def main() -> int:
         tr.close()
     if world > 1:
         dist.destroy_process_group()
-    return 0 if params_equal else 4
+    return 4 if params_equal is False else 0
 
 
 if __name__ == "__main__":

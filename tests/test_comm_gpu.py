@@ -209,7 +209,7 @@ def test_bench_native_comm_single_rank_json():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "bench.py", "--force-comm", "--batch-per-gpu", "32", "--steps", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--force-comm", "--batch-per-gpu", "32", "--steps", "2",
                         "--warmup", "1"], cwd=root, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -224,7 +224,8 @@ def test_bench_two_ranks_gloo_rehearsal_json():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = [sys.executable, "bench.py", "--gpus", "2", "--batch-per-gpu", "16", "--steps", "2", "--warmup", "1"]
+    args = [sys.executable, "bench.py", "--full", "--gpus", "2", "--batch-per-gpu", "16", "--steps", "2", "--warmup",
+            "1"]
     if torch.cuda.device_count() < 2:
         r = subprocess.run(args, cwd=root, capture_output=True, text=True, timeout=120)
         assert r.returncode != 0 and "needs 2 visible GPUs" in r.stderr

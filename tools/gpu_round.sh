@@ -87,7 +87,7 @@ for stage in "$@"; do
     rehearse4)
       # 4 DDP ranks sharing the GPU: the native C++ communicator + bucketer over the host shared-memory transport
       timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-        --master-port 29613 bench.py --gpus 4 --steps 3 --warmup 2 --dist-backend gloo --batch-per-gpu 128 \
+        --master-port 29613 bench.py --full --gpus 4 --steps 3 --warmup 2 --dist-backend gloo --batch-per-gpu 128 \
         > gpurun_out/rehearse4.log 2>&1; rc=$?
       grep metric gpurun_out/rehearse4.log
       [ $rc -eq 0 ] || { tail -30 gpurun_out/rehearse4.log; echo "rehearse4 failed rc=$rc"; exit $rc; } ;;
@@ -133,13 +133,13 @@ for stage in "$@"; do
       # 2 DDP ranks sharing the one GPU over gloo: exercises the world>1 native-trainer path
       # (bucketer, buffer broadcast, metric all-reduce, side-stream ordering) without a second GPU
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29611 bench.py --gpus 2 --steps 3 --warmup 2 --dist-backend gloo --batch-per-gpu 256 \
+        --master-port 29611 bench.py --full --gpus 2 --steps 3 --warmup 2 --dist-backend gloo --batch-per-gpu 256 \
         > gpurun_out/rehearse2.log 2>&1; rc=$?
       grep metric gpurun_out/rehearse2.log
       [ $rc -eq 0 ] || { tail -30 gpurun_out/rehearse2.log; echo "rehearse2 failed rc=$rc"; exit $rc; } ;;
     rehearse2sbn)
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29612 bench.py --gpus 2 --steps 3 --warmup 2 --dist-backend gloo --batch-per-gpu 256 \
+        --master-port 29612 bench.py --full --gpus 2 --steps 3 --warmup 2 --dist-backend gloo --batch-per-gpu 256 \
         --sync-bn --dtype fp16 > gpurun_out/rehearse2sbn.log 2>&1; rc=$?
       grep metric gpurun_out/rehearse2sbn.log
       [ $rc -eq 0 ] || { tail -30 gpurun_out/rehearse2sbn.log; echo "rehearse2sbn failed rc=$rc"; exit $rc; } ;;
