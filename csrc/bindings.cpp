@@ -25,6 +25,7 @@
 #include "kernels/conv_fwd.h"
 #include "kernels/conv_l1.h"
 #include "kernels/conv_wgrad.h"
+#include "kernels/dwconv.h"
 #include "kernels/fp32.h"
 #include "kernels/loss.h"
 #include "kernels/optim.h"
@@ -901,6 +902,68 @@ void stem_pool_bwd_reduce_out(const Tensor& dp, const Tensor& out, const Tensor&
   launched("stem_pool_bwd_reduce_out_launch");
 }
 
+// ------------------------------------------------------------------- depthwise convolution (dwconv.hip)
+// groups == Cin == Cout == C, square kernel R in {3, 5}, stride in {1, 2}, pad R / 2; x/y/dy/dx NHWC 16-bit,
+// w [R][R][C] 16-bit (taps-major); returns nothing: the caller allocates
+int dw_geom(const char* op, const Tensor& big, const Tensor& small, const Tensor* w, int64_t N, int64_t H, int64_t W,
+            int64_t C, int64_t R, int64_t stride) {
+  const int dt = dt16(big, op);
+  TORCH_CHECK(dt16(small, op) == dt && (w == nullptr || dt16(*w, op) == dt), op, ": mixed dtypes");
+  TORCH_CHECK((R == 3 || R == 5) && (stride == 1 || stride == 2), op, ": kernel size must be 3 or 5 and stride 1 or 2");
+  TORCH_CHECK(C > 0 && C % 8 == 0, op, ": C must be a positive multiple of 8, got ", C);
+  TORCH_CHECK(N >= 0 && N <= 65535 && H > 0 && W > 0 && H * W * C < (int64_t(1) << 31), op,
+              ": at most 65535 images of fewer than 2^31 elements each");
+  const int64_t P = (H - 1) / stride + 1, Q = (W - 1) / stride + 1;
+  TORCH_CHECK(big.numel() == N * H * W * C, op, ": the [N][H][W][C] operand has ", big.numel(), " elements, geometry needs ",
+              N * H * W * C);
+  TORCH_CHECK(small.numel() == N * P * Q * C, op, ": the [N][P][Q][C] operand has ", small.numel(),
+              " elements, geometry needs ", N * P * Q * C);
+  TORCH_CHECK(w == nullptr || w->numel() == R * R * C, op, ": w must hold [R][R][C] = ", R * R * C, " elements");
+  return dt;
+}
+
+void dwconv_fwd(const Tensor& x, const Tensor& w, Tensor& y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t R,
+                int64_t stride) {
+  const int dt = dw_geom("dwconv_fwd", x, y, &w, N, H, W, C, R, stride);
+  pdt::dwconv_fwd_launch(dt, p16(x, "x"), p16(w, "w"), p16(y, "y"), N, (int)H, (int)W, (int)C, (int)R, (int)stride,
+                         cur_stream());
+  launched("dwconv_fwd");
+}
+
+void dwconv_dgrad(const Tensor& dy, const Tensor& w, Tensor& dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t R,
+                  int64_t stride) {
+  const int dt = dw_geom("dwconv_dgrad", dx, dy, &w, N, H, W, C, R, stride);
+  pdt::dwconv_dgrad_launch(dt, p16(dy, "dy"), p16(w, "w"), p16(dx, "dx"), N, (int)H, (int)W, (int)C, (int)R,
+                           (int)stride, cur_stream());
+  launched("dwconv_dgrad");
+}
+
+// (splits, pix_per_split, channel groups): the caller allocates ws = [splits][R * R][C] fp32
+std::vector<int64_t> dwconv_wgrad_plan(int64_t npix, int64_t C, int64_t R, int64_t target_blocks) {
+  TORCH_CHECK((R == 3 || R == 5) && C > 0 && C % 8 == 0 && npix >= 0 && npix < (int64_t(1) << 30) &&
+                  target_blocks >= 1 && target_blocks < (int64_t(1) << 30),
+              "dwconv_wgrad_plan: bad arguments");
+  const pdt::DwWgradPlan p = pdt::dwconv_wgrad_plan(npix, (int)C, (int)R, (int)target_blocks);
+  return {p.splits, p.pix_per_split, p.groups};
+}
+
+// partial slabs ws[splits][R * R][C] (fp32) for the plan of `target_blocks`; returns the split count to pass to
+// wgrad_reduce (rows = R * R, cols = C)
+int64_t dwconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, int64_t H, int64_t W, int64_t C,
+                     int64_t R, int64_t stride, int64_t target_blocks) {
+  const int dt = dw_geom("dwconv_wgrad", x, dy, nullptr, N, H, W, C, R, stride);
+  const int64_t npix = dy.numel() / C;
+  TORCH_CHECK(npix > 0 && npix < (int64_t(1) << 30), "dwconv_wgrad: N * P * Q must be in [1, 2^30)");
+  TORCH_CHECK(target_blocks >= 1 && target_blocks < (int64_t(1) << 30), "dwconv_wgrad: bad target_blocks");
+  const pdt::DwWgradPlan p = pdt::dwconv_wgrad_plan(npix, (int)C, (int)R, (int)target_blocks);
+  TORCH_CHECK(ws.numel() >= (int64_t)p.splits * R * R * C, "dwconv_wgrad: ws holds ", ws.numel(),
+              " floats, the plan needs ", (int64_t)p.splits * R * R * C);
+  pdt::dwconv_wgrad_launch(dt, p16(x, "x"), p16(dy, "dy"), pf(ws, "ws"), N, (int)H, (int)W, (int)C, (int)R,
+                           (int)stride, p, cur_stream());
+  launched("dwconv_wgrad");
+  return p.splits;
+}
+
 // ---------------------------------------------------------------------------- VGG family (vgg.hip)
 // out = MaxPool(2, 2)(relu(y * coef[0:C] + coef[C:2C])), idx = window argmax (0..3) per pooled element (training)
 void bn_relu_maxpool2(const Tensor& y, const Tensor& coef, Tensor& out, const OptT& idx, int64_t N, int64_t H,
@@ -1537,6 +1600,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_pool_bwd_reduce", &stem_pool_bwd_reduce);
   m.def("stem_pool_bwd_reduce_out", &stem_pool_bwd_reduce_out);
   m.def("stem_pool_bwd_apply", &stem_pool_bwd_apply);
+  m.def("dwconv_fwd", &dwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("N"), py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("R"), py::arg("stride"));
+  m.def("dwconv_dgrad", &dwconv_dgrad, py::arg("dy"), py::arg("w"), py::arg("dx"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("R"), py::arg("stride"));
+  m.def("dwconv_wgrad_plan", &dwconv_wgrad_plan, py::arg("npix"), py::arg("C"), py::arg("R"), py::arg("target_blocks"));
+  m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("R"), py::arg("stride"), py::arg("target_blocks"));
   m.def("bn_relu_maxpool2", &bn_relu_maxpool2, py::arg("y"), py::arg("coef"), py::arg("out"), py::arg("idx"), py::arg("N"),
         py::arg("H"), py::arg("W"), py::arg("C"));
   m.def("maxpool2_bwd", &maxpool2_bwd);

@@ -155,6 +155,10 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
     g.add_argument("--autotune", default=False, type=str2bool, nargs="?", const=True,
                    help="time the candidate conv tile configs once per shape and keep the fastest (the analogue of "
                         "the reference's cudnn.benchmark=True); off = the static per-shape table")
+    g.add_argument("--native-depthwise", default="off", choices=["off", "on"],
+                   help="torch engine: run qualifying depthwise convs (3x3 / 5x5, stride 1 / 2, no bias, channels % 8 "
+                        "== 0) on the native HIP depthwise kernels where the activations are 16-bit channels_last "
+                        "GPU tensors; elsewhere (CPU, fp32, validation) the modules fall back to F.conv2d")
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

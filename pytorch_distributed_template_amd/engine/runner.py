@@ -335,6 +335,11 @@ def main(mode: str, argv: Optional[list] = None) -> int:
 
     ddp_print("=> engine: {} | compute dtype: {} | device: {} | world: {}".format(engine, str(dtype).split(".")[-1],
                                                                                 device, world), logger, rank)
+    if getattr(args, "native_depthwise", "off") == "on" and engine == "torch":
+        # before the trainer flattens the parameters: the converted modules keep the same Parameter objects
+        from ..ops.depthwise import convert_depthwise
+        ddp_print("=> native depthwise: {} conv(s) of {} converted".format(convert_depthwise(model), args.arch),
+                  logger, rank)
     trainer = build_trainer(mode, model, args, device, dtype, engine, world)
     optimizer = trainer.optimizer
     gn = getattr(args, "gpu_normalize", "off")

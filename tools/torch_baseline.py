@@ -15,6 +15,8 @@ p.add_argument("--steps", type=int, default=10)
 p.add_argument("--dtype", default="bf16")
 p.add_argument("--benchmark", type=int, default=1, help="cudnn.benchmark (MIOpen search) as the reference sets it")
 p.add_argument("--cl", type=int, default=1)
+p.add_argument("--native-depthwise", default="off", choices=["off", "on"],
+               help="on: qualifying depthwise convs run on the native HIP kernels (ops/depthwise.py); off: MIOpen")
 a = p.parse_args()
 torch.backends.cudnn.benchmark = bool(a.benchmark)
 import threading
@@ -29,6 +31,11 @@ def _heartbeat():  # MIOpen's search can stay silent for minutes: keep the run v
 threading.Thread(target=_heartbeat, daemon=True).start()
 dev = torch.device("cuda:0")
 m = registry.create(a.arch).to(dev)
+n_dw = 0
+if a.native_depthwise == "on":
+    from pytorch_distributed_template_amd.ops.depthwise import convert_depthwise
+    n_dw = convert_depthwise(m)
+    print(f"native depthwise: {n_dw} conv(s) converted", flush=True)
 if a.cl:
     m = m.to(memory_format=torch.channels_last)
 opt = torch.optim.SGD(m.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4)
@@ -57,5 +64,6 @@ for _ in range(a.steps):
     print(".", end="", flush=True)
 print()
 el = (time.time() - t) / a.steps
-print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl, "ms_per_step": el * 1e3,
+print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl,
+                  "native_depthwise": a.native_depthwise, "depthwise_converted": n_dw, "ms_per_step": el * 1e3,
                   "img_per_s": a.bs / el, "max_mem_GB": torch.cuda.max_memory_allocated() / 1e9}))
