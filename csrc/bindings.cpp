@@ -19,6 +19,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "common.h"
 #include "dtypes.h"
 #include "kernels/bn.h"
 #include "kernels/conv1x1.h"
@@ -143,6 +144,43 @@ double* pd(const Tensor& t, const char* name) {
 }
 
 // ------------------------------------------------------------------------------------------ conv
+// Plain forward convolution: in = i * stride - pad + t, the GEMM grid is the whole Pm x Qm output (the caller sets cs).
+void set_fwd_geom(pdt::ConvGeom& a, int64_t N, int64_t H, int64_t W, int64_t C, int64_t Kout, int64_t T, int64_t U,
+                  int64_t Pm, int64_t Qm, int64_t stride, int64_t pad) {
+  a.N = N; a.H = H; a.W = W; a.C = C; a.Kout = Kout; a.T = T; a.U = U; a.Pm = Pm; a.Qm = Qm;
+  a.ist_h = stride; a.ist_w = stride; a.ioff_h = -pad; a.ioff_w = -pad; a.tstep_h = 1; a.tstep_w = 1;
+  a.OH = Pm; a.OW = Qm; a.ost_h = 1; a.ost_w = 1; a.ooff_h = 0; a.ooff_w = 0;
+  a.M = N * Pm * Qm;
+}
+
+// Backward-data of a (strided) conv as one multi-phase launch over dY [N,P,Q,K] -> dX [N,H,W,C] (the caller sets cs):
+// phases = [(ph, pw, T, U, ioff_h, ioff_w, woff), ...], phase i writing the output pixels (ph + stride * .,
+// pw + stride * .) from its [C][T][U][K] weights at element woff of a tensor of w_numel elements -- of each of the
+// nslice channel slices' tensors, w_slice_stride elements apart (dense convs: 1 / 0).
+void set_dgrad_geom(const char* op, pdt::ConvGeom& a, int64_t N, int64_t P, int64_t Q, int64_t K, int64_t C, int64_t H,
+                    int64_t W, int64_t stride, const std::vector<std::vector<int64_t>>& phases, int64_t w_numel,
+                    int64_t nslice, int64_t w_slice_stride) {
+  TORCH_CHECK(!phases.empty() && phases.size() <= 4, op, ": 1..4 phases");
+  a.N = N; a.H = P; a.W = Q; a.C = K; a.Kout = C;
+  a.ist_h = 1; a.ist_w = 1; a.tstep_h = -1; a.tstep_w = -1;
+  a.OH = H; a.OW = W; a.ost_h = stride; a.ost_w = stride;
+  a.nphase = (int)phases.size();
+  int64_t maxM = 0;
+  for (size_t i = 0; i < phases.size(); ++i) {
+    const auto& f = phases[i];
+    TORCH_CHECK(f.size() == 7, op, ": phase = (ph, pw, T, U, ioff_h, ioff_w, woff)");
+    const int64_t Pm = (H - f[0] + stride - 1) / stride, Qm = (W - f[1] + stride - 1) / stride;
+    TORCH_CHECK(Pm > 0 && Qm > 0 && f[6] + C * f[2] * f[3] * K + (nslice - 1) * w_slice_stride <= w_numel, op,
+                ": bad phase");
+    a.pooff_h[i] = (int)f[0]; a.pooff_w[i] = (int)f[1]; a.pT[i] = (int)f[2]; a.pU[i] = (int)f[3];
+    a.pioff_h[i] = (int)f[4]; a.pioff_w[i] = (int)f[5]; a.pwoff[i] = f[6];
+    a.pPm[i] = (int)Pm; a.pQm[i] = (int)Qm;
+    maxM = std::max(maxM, N * Pm * Qm);
+  }
+  TORCH_CHECK(maxM < (int64_t(1) << 31), op, ": N*Pm*Qm must be < 2^31 (32-bit pixel indexing)");
+  a.M = maxM;
+}
+
 void conv_fwd(const Tensor& x, const Tensor& w, Tensor& y, const OptT& res, const OptT& stats, int64_t N, int64_t H,
               int64_t W, int64_t C, int64_t Kout, int64_t T, int64_t U, int64_t Pm, int64_t Qm, int64_t ist_h,
               int64_t ist_w, int64_t ioff_h, int64_t ioff_w, int64_t tstep_h, int64_t tstep_w, int64_t OH, int64_t OW,
@@ -199,9 +237,8 @@ void conv_fwd(const Tensor& x, const Tensor& w, Tensor& y, const OptT& res, cons
 // y = conv(relu(bn(z))) with BN statistics of y, and relu(bn(z)) never written.
 bool conv_fwd_pre_supported(int64_t N, int64_t H, int64_t W) {
   pdt::ConvFwdArgs a{};
-  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.C = 64; a.Kout = 64; a.T = 3; a.U = 3; a.cs = 64;
-  a.Pm = (int)H; a.Qm = (int)W; a.ist_h = 1; a.ist_w = 1; a.ioff_h = -1; a.ioff_w = -1; a.tstep_h = 1;
-  a.tstep_w = 1; a.OH = (int)H; a.OW = (int)W; a.ost_h = 1; a.ost_w = 1;
+  set_fwd_geom(a, N, H, W, 64, 64, 3, 3, H, W, 1, 1);
+  a.cs = 64;
   int flip = 0;
   return pdt::conv_l1_eligible(a, &flip);
 }
@@ -222,10 +259,8 @@ void conv_fwd_pre(const Tensor& z, const Tensor& w, Tensor& y, const Tensor& sta
   a.y = p16(y, "y");
   a.stats = pd(stats, "stats");
   a.pre_coef = pf(pre_coef, "pre_coef");
-  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.C = 64; a.Kout = 64; a.T = 3; a.U = 3; a.cs = 64;
-  a.Pm = (int)H; a.Qm = (int)W; a.ist_h = 1; a.ist_w = 1; a.ioff_h = -1; a.ioff_w = -1; a.tstep_h = 1;
-  a.tstep_w = 1; a.OH = (int)H; a.OW = (int)W; a.ost_h = 1; a.ost_w = 1;
-  a.M = N * H * W;
+  set_fwd_geom(a, N, H, W, 64, 64, 3, 3, H, W, 1, 1);
+  a.cs = 64;
   pdt::conv_fwd_launch(a, dt, 256, 64, 64, cur_stream());
   launched("conv_fwd_launch");
 }
@@ -263,9 +298,9 @@ int64_t conv_m_tiles(int64_t M, int64_t bm) { return pdt::conv_fwd_m_tiles(M, (i
 // Which persistent 1x1 backward-data kernel conv_dgrad_impl runs for a launch, if any: 0 none (tiled implicit GEMM),
 // 1 conv1x1.hip (C = 256 -> K = 64 | 128), 2 conv1x1x.hip (sliced, layers 2-4).  The ONE source of this dispatch: the
 // executor asks it (conv_dgrad_persistent) before choosing / autotuning a tile, so the two cannot drift apart.
-static int dgrad_persistent_kind(int64_t K, int64_t C, int64_t bnb, int64_t stride,
-                                 const std::vector<std::vector<int64_t>>& phases, int64_t H, int64_t W, int64_t P,
-                                 int64_t Q, int64_t res_phase) {
+int64_t dgrad_persistent_kind(int64_t K, int64_t C, int64_t bnb, int64_t stride,
+                              const std::vector<std::vector<int64_t>>& phases, int64_t H, int64_t W, int64_t P,
+                              int64_t Q, int64_t res_phase) {
   if (!(bnb == 2 || bnb == 3) || res_phase >= 0 || stride != 1 || phases.size() != 1 || H != P || W != Q) return 0;
   const auto& f = phases[0];
   if (f.size() < 6 || f[0] != 0 || f[1] != 0 || f[2] != 1 || f[3] != 1 || f[4] != 0 || f[5] != 0) return 0;
@@ -274,12 +309,6 @@ static int dgrad_persistent_kind(int64_t K, int64_t C, int64_t bnb, int64_t stri
       !(pdt::conv1x1x_prefer_l1() && x_ok))
     return 1;
   return x_ok ? 2 : 0;
-}
-
-int64_t conv_dgrad_persistent(int64_t K, int64_t C, int64_t bnb, int64_t stride,
-                              const std::vector<std::vector<int64_t>>& phases, int64_t H, int64_t W, int64_t P,
-                              int64_t Q, int64_t res_phase) {
-  return dgrad_persistent_kind(K, C, bnb, stride, phases, H, W, P, Q, res_phase);
 }
 
 // Backward-data of a (strided) conv in ONE launch: phases = [(ph, pw, T, U, ioff_h, ioff_w, woff), ...]
@@ -294,23 +323,22 @@ void conv_dgrad_impl(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT&
   TORCH_CHECK(dy.numel() == N * P * Q * K && dx.numel() == N * H * W * C, "conv_dgrad: size mismatch");
   TORCH_CHECK(dy.numel() < (int64_t(1) << 30) && wt.numel() < (int64_t(1) << 30),
               "conv_dgrad: operands exceed 2 GiB (32-bit buffer offsets)");
-  TORCH_CHECK(!phases.empty() && phases.size() <= 4, "conv_dgrad: 1..4 phases");
   TORCH_CHECK(K % bk == 0 && C % bn == 0, "conv_dgrad: K % bk / C % bn must be 0");
   pdt::ConvFwdArgs a{};
   a.x = p16(dy, "dy");
   a.w = p16(wt, "wt");
   a.y = p16(dx, "dx");
+  set_dgrad_geom("conv_dgrad", a, N, P, Q, K, C, H, W, stride, phases, wt.numel(), 1, 0);
+  a.cs = K;
   TORCH_CHECK(res_phase < (int64_t)phases.size() && (res_phase < 0 || res.has_value()), "conv_dgrad: bad res_phase");
   if (res.has_value()) {
     if (res_phase >= 0) {  // compact residual of one phase: [N * Pm * Qm][C] of that phase
-      const auto& f = phases[res_phase];
-      TORCH_CHECK(f.size() == 7, "conv_dgrad: phase = (ph, pw, T, U, ioff_h, ioff_w, woff)");
-      const int64_t Pm = (H - f[0] + stride - 1) / stride, Qm = (W - f[1] + stride - 1) / stride;
+      const int64_t Pm = a.pPm[res_phase], Qm = a.pQm[res_phase];
       TORCH_CHECK(res->numel() == N * Pm * Qm * C, "conv_dgrad: compact residual size mismatch");
       // every phase reads the compact residual unconditionally (its add is selected per phase): its rows must
       // cover every phase's GEMM rows
-      for (const auto& g : phases)
-        TORCH_CHECK(g.size() == 7 && ((H - g[0] + stride - 1) / stride) * ((W - g[1] + stride - 1) / stride) <= Pm * Qm,
+      for (int i = 0; i < a.nphase; ++i)
+        TORCH_CHECK((int64_t)a.pPm[i] * a.pQm[i] <= Pm * Qm,
                     "conv_dgrad: the compact residual's phase must be the largest");
     } else {
       TORCH_CHECK(res->numel() == dx.numel(), "conv_dgrad: residual size mismatch");
@@ -319,24 +347,6 @@ void conv_dgrad_impl(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT&
     a.res = p16(*res, "res");
   }
   a.res_phase = (int)res_phase;
-  a.N = N; a.H = P; a.W = Q; a.C = K; a.cs = K; a.Kout = C;
-  a.ist_h = 1; a.ist_w = 1; a.tstep_h = -1; a.tstep_w = -1;
-  a.OH = H; a.OW = W; a.ost_h = stride; a.ost_w = stride;
-  a.nphase = (int)phases.size();
-  int64_t maxM = 0;
-  for (size_t i = 0; i < phases.size(); ++i) {
-    const auto& f = phases[i];
-    TORCH_CHECK(f.size() == 7, "conv_dgrad: phase = (ph, pw, T, U, ioff_h, ioff_w, woff)");
-    const int64_t ph = f[0], pw = f[1];
-    const int64_t Pm = (H - ph + stride - 1) / stride, Qm = (W - pw + stride - 1) / stride;
-    TORCH_CHECK(Pm > 0 && Qm > 0 && f[6] + C * f[2] * f[3] * K <= wt.numel(), "conv_dgrad: bad phase");
-    a.pooff_h[i] = (int)ph; a.pooff_w[i] = (int)pw; a.pT[i] = (int)f[2]; a.pU[i] = (int)f[3];
-    a.pioff_h[i] = (int)f[4]; a.pioff_w[i] = (int)f[5]; a.pwoff[i] = f[6];
-    a.pPm[i] = (int)Pm; a.pQm[i] = (int)Qm;
-    maxM = std::max(maxM, N * Pm * Qm);
-  }
-  TORCH_CHECK(maxM < (int64_t(1) << 31), "conv_dgrad: N*Pm*Qm must be < 2^31 (32-bit pixel indexing)");
-  a.M = maxM;
   if (bnb != 0) {
     // fused BN-backward reduce of the BatchNorm that consumes dx (see conv_fwd.h)
     TORCH_CHECK(bnb >= 1 && bnb <= 3, "conv_dgrad: bnb must be 0..3");
@@ -358,31 +368,24 @@ void conv_dgrad_impl(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT&
     a.bn_mask = pmask(bn_mask, dx.numel(), "bn_mask");
     a.stats = pd(*bn_slots, "bn_slots");
   }
-  const int pk = dgrad_persistent_kind(K, C, bnb, stride, phases, H, W, P, Q, res_phase);
+  const int64_t pk = dgrad_persistent_kind(K, C, bnb, stride, phases, H, W, P, Q, res_phase);
   if (pk == 1) {
-    const auto& f = phases[0];
-    {
-      // 1x1 256 -> 64 | 128 conv's backward-data with the block-output BN-backward epilogue: persistent kernel
-      // (conv1x1.hip);
-      // its [256][K] weights start at the phase's offset (bounds checked with the phases above)
-      pdt::conv1x1_c64_bnb_launch(a.x, a.w + f[6], a.y, a.res, a.bn_y1, a.bn_coef1, bnb == 3 ? a.bn_y2 : nullptr,
-                                  bnb == 3 ? a.bn_coef2 : nullptr, a.bn_mask, a.stats, N * P * Q, (int)K, dt,
-                                  cur_stream());
-      launched("conv1x1_c64_bnb");
-      return;
-    }
+    // 1x1 256 -> 64 | 128 conv's backward-data with the block-output BN-backward epilogue: persistent kernel
+    // (conv1x1.hip); its [256][K] weights start at the phase's offset (bounds checked with the phases above)
+    pdt::conv1x1_c64_bnb_launch(a.x, a.w + a.pwoff[0], a.y, a.res, a.bn_y1, a.bn_coef1, bnb == 3 ? a.bn_y2 : nullptr,
+                                bnb == 3 ? a.bn_coef2 : nullptr, a.bn_mask, a.stats, N * P * Q, (int)K, dt,
+                                cur_stream());
+    launched("conv1x1_c64_bnb");
+    return;
   }
   if (pk == 2) {
-    const auto& f = phases[0];
-    {
-      // ResNet-50 layers 2-4: 1x1 C -> 4C backward-data (conv1 of a bottleneck) with the block-output BN-backward
-      // epilogue on the persistent sliced kernel (conv1x1x.hip); [C][K] weights at the phase's offset
-      pdt::conv1x1x_bnb_launch(a.x, a.w + f[6], a.y, a.res, a.bn_y1, a.bn_coef1, bnb == 3 ? a.bn_y2 : nullptr,
-                               bnb == 3 ? a.bn_coef2 : nullptr, a.bn_mask, a.stats, N * P * Q, (int)K, (int)C, dt,
-                               cur_stream());
-      launched("conv1x1x_bnb");
-      return;
-    }
+    // ResNet-50 layers 2-4: 1x1 C -> 4C backward-data (conv1 of a bottleneck) with the block-output BN-backward
+    // epilogue on the persistent sliced kernel (conv1x1x.hip); [C][K] weights at the phase's offset
+    pdt::conv1x1x_bnb_launch(a.x, a.w + a.pwoff[0], a.y, a.res, a.bn_y1, a.bn_coef1, bnb == 3 ? a.bn_y2 : nullptr,
+                             bnb == 3 ? a.bn_coef2 : nullptr, a.bn_mask, a.stats, N * P * Q, (int)K, (int)C, dt,
+                             cur_stream());
+    launched("conv1x1x_bnb");
+    return;
   }
   pdt::conv_fwd_launch(a, dt, (int)bm, (int)bn, (int)bk, cur_stream());
   launched("conv_fwd_launch");
@@ -502,11 +505,6 @@ void conv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, int64_
 // row stride = the full width's).  The MFMA work is S / cg times the grouped FLOPs (16x at cg = 4 ... 2x at 32), in
 // exchange for running on the tuned tiles with the fused statistics / BN-backward epilogues.
 static constexpr int64_t kGSlice = 64;
-#define PDT_BCOUNT(name)                                                  \
-  do {                                                                    \
-    static long long* _c = pdt::dispatch_counter(name);                   \
-    __atomic_fetch_add(_c, 1LL, __ATOMIC_RELAXED);                        \
-  } while (0)
 
 void gconv_fwd(const Tensor& x, const Tensor& wslice, Tensor& y, const OptT& stats, int64_t N, int64_t H, int64_t W,
                int64_t width, int64_t R, int64_t stride, int64_t pad, int64_t P, int64_t Q, int64_t j, int64_t bm,
@@ -535,14 +533,12 @@ void gconv_fwd(const Tensor& x, const Tensor& wslice, Tensor& y, const OptT& sta
     a.stats = pd(*stats, "stats") + j0 * S * 2;
     a.stats_ld = (int)(width * 2);
   }
-  a.N = N; a.H = H; a.W = W; a.C = S; a.Kout = S; a.T = R; a.U = R; a.Pm = P; a.Qm = Q; a.cs = width;
+  set_fwd_geom(a, N, H, W, S, S, R, R, P, Q, stride, pad);
+  a.cs = width;
   a.ldy = (int)width;
-  a.ist_h = stride; a.ist_w = stride; a.ioff_h = -pad; a.ioff_w = -pad; a.tstep_h = 1; a.tstep_w = 1;
-  a.OH = P; a.OW = Q; a.ost_h = 1; a.ost_w = 1; a.ooff_h = 0; a.ooff_w = 0;
-  a.M = N * P * Q;
   pdt::conv_fwd_launch(a, dt, (int)bm, (int)bn, 64, cur_stream());
   launched("gconv_fwd");
-  PDT_BCOUNT("gconv_fwd");
+  PDT_COUNT("gconv_fwd");
 }
 
 // backward data of slice j (phases and their derived-weight offsets as conv_dgrad), optionally with the fused
@@ -560,7 +556,7 @@ void gconv_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, int64_t N, int6
   const int64_t wstride = S * S * taps;  // elements of one slice's derived phase weights
   TORCH_CHECK(dy.numel() == N * P * Q * width && dx.numel() == N * H * W * width, "gconv_dgrad: size mismatch");
   TORCH_CHECK(dy.numel() < (int64_t(1) << 30) && dx.numel() < (int64_t(1) << 30), "gconv_dgrad: operands exceed 2 GiB");
-  TORCH_CHECK(!phases.empty() && phases.size() <= 4 && S % bn == 0, "gconv_dgrad: 1..4 phases / tile");
+  TORCH_CHECK(S % bn == 0, "gconv_dgrad: tile");
   pdt::ConvFwdArgs a{};
   a.x = p16(dy, "dy") + j0 * S;
   a.w = p16(wt, "wt");
@@ -569,26 +565,10 @@ void gconv_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, int64_t N, int6
     a.nslice = (int)nsl;
     a.slice_wstride = wstride;
   }
-  a.N = N; a.H = P; a.W = Q; a.C = S; a.cs = width; a.Kout = S; a.ldy = (int)width;
-  a.ist_h = 1; a.ist_w = 1; a.tstep_h = -1; a.tstep_w = -1;
-  a.OH = H; a.OW = W; a.ost_h = stride; a.ost_w = stride;
-  a.nphase = (int)phases.size();
-  a.res_phase = -1;
-  int64_t maxM = 0;
-  for (size_t i = 0; i < phases.size(); ++i) {
-    const auto& f = phases[i];
-    TORCH_CHECK(f.size() == 7, "gconv_dgrad: phase = (ph, pw, T, U, ioff_h, ioff_w, woff)");
-    const int64_t ph = f[0], pw = f[1];
-    const int64_t Pm = (H - ph + stride - 1) / stride, Qm = (W - pw + stride - 1) / stride;
-    TORCH_CHECK(Pm > 0 && Qm > 0 && f[6] + S * f[2] * f[3] * S + (nsl - 1) * wstride <= wt.numel(),
-                "gconv_dgrad: bad phase");
-    a.pooff_h[i] = (int)ph; a.pooff_w[i] = (int)pw; a.pT[i] = (int)f[2]; a.pU[i] = (int)f[3];
-    a.pioff_h[i] = (int)f[4]; a.pioff_w[i] = (int)f[5]; a.pwoff[i] = f[6];
-    a.pPm[i] = (int)Pm; a.pQm[i] = (int)Qm;
-    maxM = std::max(maxM, N * Pm * Qm);
-  }
-  TORCH_CHECK(maxM < (int64_t(1) << 31), "gconv_dgrad: 32-bit pixel indexing");
-  a.M = maxM;
+  // one slice is a dense S -> S conv; the pixel strides are the full width's
+  set_dgrad_geom("gconv_dgrad", a, N, P, Q, S, S, H, W, stride, phases, wt.numel(), nsl, wstride);
+  a.cs = width;
+  a.ldy = (int)width;
   if (bn_y1.has_value()) {  // bnb 1: ReLU mask from y1 and the forward coefficients; dx holds dz
     TORCH_CHECK(bn_coef1.has_value() && bn_slots.has_value() && bn_y1->numel() == dx.numel() &&
                     dt16(*bn_y1, "bn_y1") == dt && bn_coef1->numel() >= 4 * width &&
@@ -603,7 +583,7 @@ void gconv_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, int64_t N, int6
   }
   pdt::conv_fwd_launch(a, dt, (int)bm, (int)bn, 64, cur_stream());
   launched("gconv_dgrad");
-  PDT_BCOUNT("gconv_dgrad");
+  PDT_COUNT("gconv_dgrad");
 }
 
 // weight gradient of slice j: the dense S x (R*R*S) partials [splits][S][ldw] (the executor keeps the diagonal blocks)
@@ -631,7 +611,7 @@ void gconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, int64
   TORCH_CHECK(a.tile == 64 && pix_per_split % 128 == 0 && splits * pix_per_split >= a.P, "gconv_wgrad: bad plan");
   pdt::conv_wgrad_launch(a, dt, cur_stream());
   launched("gconv_wgrad");
-  PDT_BCOUNT("gconv_wgrad");
+  PDT_COUNT("gconv_wgrad");
 }
 
 // ResNet stem weight gradient with its dY computed in-kernel (max-pool backward + ReLU mask + BN-backward
@@ -731,7 +711,7 @@ int64_t gconv_wgrad_l1(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N,
     written = pdt::wgrad3x3_c64_launch(a, blocks, dt, cur_stream());
   }
   launched("gconv_wgrad_l1");
-  PDT_BCOUNT("gconv_wgrad_l1");
+  PDT_COUNT("gconv_wgrad_l1");
   return written;
 }
 
@@ -1215,10 +1195,7 @@ void conv32_fwd(const Tensor& x, const Tensor& w, Tensor& y, const OptT& res, co
     TORCH_CHECK(stats->numel() >= pdt::kStatSlots * Kout * 2, "conv32_fwd: stats buffer too small");
     a.stats = pd(*stats, "stats");
   }
-  a.N = N; a.H = H; a.W = W; a.C = C; a.Kout = Kout; a.T = T; a.U = U; a.Pm = Pm; a.Qm = Qm;
-  a.ist_h = stride; a.ist_w = stride; a.ioff_h = -pad; a.ioff_w = -pad; a.tstep_h = 1; a.tstep_w = 1;
-  a.OH = Pm; a.OW = Qm; a.ost_h = 1; a.ost_w = 1; a.ooff_h = 0; a.ooff_w = 0;
-  a.M = N * Pm * Qm;
+  set_fwd_geom(a, N, H, W, C, Kout, T, U, Pm, Qm, stride, pad);
   pdt::conv32_launch(a, (int)bm, (int)bn, cur_stream());
   launched("conv32_launch");
 }
@@ -1232,7 +1209,6 @@ void conv32_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT& re
   TORCH_CHECK(dy.numel() == N * P * Q * K && dx.numel() == N * H * W * C, "conv32_dgrad: size mismatch");
   TORCH_CHECK(K % 32 == 0 && C % bn == 0, "conv32_dgrad: K % 32 / C % bn must be 0");
   TORCH_CHECK(dy.numel() < (int64_t(1) << 30) && wt.numel() < (int64_t(1) << 30), "conv32_dgrad: operands too large");
-  TORCH_CHECK(!phases.empty() && phases.size() <= 4, "conv32_dgrad: 1..4 phases");
   pdt::Conv32Args a{};
   a.x = pf(dy, "dy"); a.w = pf(wt, "wt"); a.y = pf(dx, "dx");
   if (res.has_value()) {
@@ -1257,23 +1233,7 @@ void conv32_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT& re
       a.bn_y2 = pf(*bn_y2, "bn_y2"); a.bn_coef2 = pf(*bn_coef2, "bn_coef2");
     }
   }
-  a.N = N; a.H = P; a.W = Q; a.C = K; a.Kout = C;
-  a.ist_h = 1; a.ist_w = 1; a.tstep_h = -1; a.tstep_w = -1;
-  a.OH = H; a.OW = W; a.ost_h = stride; a.ost_w = stride;
-  a.nphase = (int)phases.size();
-  int64_t maxM = 0;
-  for (size_t i = 0; i < phases.size(); ++i) {
-    const auto& f = phases[i];
-    TORCH_CHECK(f.size() == 7, "conv32_dgrad: phase = (ph, pw, T, U, ioff_h, ioff_w, woff)");
-    const int64_t Pm = (H - f[0] + stride - 1) / stride, Qm = (W - f[1] + stride - 1) / stride;
-    TORCH_CHECK(Pm > 0 && Qm > 0 && f[6] + C * f[2] * f[3] * K <= wt.numel(), "conv32_dgrad: bad phase");
-    a.pooff_h[i] = (int)f[0]; a.pooff_w[i] = (int)f[1]; a.pT[i] = (int)f[2]; a.pU[i] = (int)f[3];
-    a.pioff_h[i] = (int)f[4]; a.pioff_w[i] = (int)f[5]; a.pwoff[i] = f[6];
-    a.pPm[i] = (int)Pm; a.pQm[i] = (int)Qm;
-    maxM = std::max(maxM, N * Pm * Qm);
-  }
-  TORCH_CHECK(maxM < (int64_t(1) << 31), "conv32_dgrad: too many pixels");
-  a.M = maxM;
+  set_dgrad_geom("conv32_dgrad", a, N, P, Q, K, C, H, W, stride, phases, wt.numel(), 1, 0);
   a.Pm = a.pPm[0]; a.Qm = a.pQm[0];
   pdt::conv32_launch(a, (int)bm, (int)bn, cur_stream());
   launched("conv32_launch");
@@ -1569,7 +1529,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd_pre", &conv_fwd_pre);
   m.def("conv1x1x", &conv1x1x);
   m.def("conv1x1x_supported", &conv1x1x_supported);
-  m.def("conv_dgrad_persistent", &conv_dgrad_persistent);
+  m.def("conv_dgrad_persistent", &dgrad_persistent_kind);
   m.def("conv1x1x_mode", &conv1x1x_mode);
   m.def("conv1x1x_l1_mode", &conv1x1x_l1_mode);
   m.def("conv_fwd_pre_supported", &conv_fwd_pre_supported);

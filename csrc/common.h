@@ -8,6 +8,27 @@
 
 #include "dtypes.h"
 
+namespace pdt {
+
+// Exact unsigned division by a runtime constant for dividends < 2^31: q = umulhi(x, mul) >> shift
+// (mul = ceil(2^(32+s)/d), s = floor(log2 d)); powers of two use mul = 0 (plain shift).
+struct FastDiv {
+  uint32_t mul;
+  uint32_t shift;
+};
+
+inline FastDiv make_fastdiv(uint32_t d) {
+  uint32_t s = 0;
+  while ((2ull << s) <= d) ++s;
+  if ((d & (d - 1)) == 0) return FastDiv{0u, s};
+  const uint64_t m = ((1ull << (32 + s)) + d - 1) / d;
+  return FastDiv{(uint32_t)m, s};
+}
+
+}  // namespace pdt
+
+// ---- device code: the kernels only (the host C++ compiler of the bindings sees the host half of this header)
+#ifdef __HIPCC__
 #define PDT_DEVICE __device__ __forceinline__
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -142,21 +163,6 @@ PDT_DEVICE float wave_max(float v) {
   return v;
 }
 
-// Exact unsigned division by a runtime constant for dividends < 2^31: q = umulhi(x, mul) >> shift
-// (mul = ceil(2^(32+s)/d), s = floor(log2 d)); powers of two use mul = 0 (plain shift).
-struct FastDiv {
-  uint32_t mul;
-  uint32_t shift;
-};
-
-inline FastDiv make_fastdiv(uint32_t d) {
-  uint32_t s = 0;
-  while ((2ull << s) <= d) ++s;
-  if ((d & (d - 1)) == 0) return FastDiv{0u, s};
-  const uint64_t m = ((1ull << (32 + s)) + d - 1) / d;
-  return FastDiv{(uint32_t)m, s};
-}
-
 PDT_DEVICE uint32_t fdiv(uint32_t x, FastDiv f) {
   return f.mul ? (__umulhi(x, f.mul) >> f.shift) : (x >> f.shift);
 }
@@ -215,6 +221,7 @@ PDT_DEVICE int xcd_remap(int bid, int nwg) {
 }
 
 }  // namespace pdt
+#endif  // __HIPCC__
 
 #define PDT_HIP_CHECK(expr)                                                        \
   do {                                                                             \

@@ -401,21 +401,9 @@ void conv_fwd_kernel(ConvFwdArgs args) {
     if (a.bn_coef1 != nullptr) a.bn_coef1 += sl * a.Kout;
     a.srows_coff = sl * a.Kout;
   }
-  if (args.nphase > 0) {  // multi-phase launch: this block's phase geometry (wave-uniform)
-    const int ph = blockIdx.y;
-    a.T = args.pT[ph]; a.U = args.pU[ph];
-    a.ioff_h = args.pioff_h[ph]; a.ioff_w = args.pioff_w[ph];
-    a.Pm = args.pPm[ph]; a.Qm = args.pQm[ph];
-    a.ooff_h = args.pooff_h[ph]; a.ooff_w = args.pooff_w[ph];
-    a.m_tiles = args.pmt[ph];
-    a.M = (int64_t)a.N * a.Pm * a.Qm;
-    a.w = wbase + args.pwoff[ph];
-    a.pq_mul = args.ppq_mul[ph]; a.pq_shift = args.ppq_shift[ph];
-    a.q_mul = args.pq1_mul[ph]; a.q_shift = args.pq1_shift[ph];
-    if ((int)blockIdx.x >= a.m_tiles * a.n_tiles) {
-      zero_stat_row<EPI, BN>(a, NW * 64);
-      return;
-    }
+  if (args.nphase > 0 && !select_phase(a, args, wbase, blockIdx.y)) {  // multi-phase launch: this block's phase
+    zero_stat_row<EPI, BN>(a, NW * 64);
+    return;
   }
   using E = E16<DT>;
   typedef typename E::vec8 vec8;
@@ -640,21 +628,9 @@ PDT_DEVICE void vm_wait() {
 template <int DT, int BM, int BN, int EPI, int RES, bool PP_STAGE = (EPI != 2)>  // (EPI 2 + staging spills)
 __global__ __launch_bounds__(512) void conv_pp_kernel(ConvFwdArgs args) {
   ConvFwdArgs a = args;
-  if (args.nphase > 0) {  // multi-phase launch (strided backward-data): this block's phase geometry
-    const int ph = blockIdx.y;
-    a.T = args.pT[ph]; a.U = args.pU[ph];
-    a.ioff_h = args.pioff_h[ph]; a.ioff_w = args.pioff_w[ph];
-    a.Pm = args.pPm[ph]; a.Qm = args.pQm[ph];
-    a.ooff_h = args.pooff_h[ph]; a.ooff_w = args.pooff_w[ph];
-    a.m_tiles = args.pmt[ph];
-    a.M = (int64_t)a.N * a.Pm * a.Qm;
-    a.w = args.w + args.pwoff[ph];
-    a.pq_mul = args.ppq_mul[ph]; a.pq_shift = args.ppq_shift[ph];
-    a.q_mul = args.pq1_mul[ph]; a.q_shift = args.pq1_shift[ph];
-    if ((int)blockIdx.x >= a.m_tiles * a.n_tiles) {
-      zero_stat_row<EPI, BN>(a, 512);
-      return;
-    }
+  if (args.nphase > 0 && !select_phase(a, args, args.w, blockIdx.y)) {  // strided backward-data: this block's phase
+    zero_stat_row<EPI, BN>(a, 512);
+    return;
   }
   using E = E16<DT>;
   typedef typename E::vec8 vec8;
@@ -849,7 +825,7 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvFwdArgs args) {
 }
 
 template <int DT, int BM, int BN>
-static void launch_pp(const ConvFwdArgs& args, hipStream_t s) {
+static void launch_pp(const ConvFwdArgs& args, int gx, hipStream_t s) {
   // the ping-pong kernel stores straight from the accumulators: with the PERM epilogue the direct stores are 16 bytes
   // per lane, and LDS-staged row stores (one wave row-group at a time) measured slower on the same box in round 5
   // (ResNet-18 20.45/20.43 -> 20.33/20.32 ms, ResNet-50 73.23/73.36 -> 73.09/73.19); that knob was removed in round 6
@@ -858,11 +834,6 @@ static void launch_pp(const ConvFwdArgs& args, hipStream_t s) {
   if (a.nslice > 1)
     pdt_hip_fail("conv_pp: slice-batched (grouped) launches run on the generic kernel", hipErrorInvalidValue, __FILE__,
                  __LINE__);
-  int gx = a.m_tiles * a.n_tiles;
-  if (a.nphase > 0) {
-    gx = 0;
-    for (int p = 0; p < a.nphase; ++p) gx = gx > a.pmt[p] * a.n_tiles ? gx : a.pmt[p] * a.n_tiles;
-  }
   dim3 grid(gx, a.nphase > 0 ? a.nphase : 1), block(512);
   const int rs = a.res == nullptr ? 0 : (a.res_phase >= 0 && a.nphase > 0 ? 2 : 1);
   const int epi = a.bnb ? a.bnb + 1 : (a.stats != nullptr ? 1 : 0);
@@ -885,12 +856,7 @@ static void launch_pp(const ConvFwdArgs& args, hipStream_t s) {
 
 // ----------------------------------------------------------------------------------------------
 template <int DT, int BM, int BN, int BK, int WAVES_N, int STAGES, int NW>
-static void launch_cfg(const ConvFwdArgs& a, hipStream_t s) {
-  int gx = a.m_tiles * a.n_tiles;
-  if (a.nphase > 0) {
-    gx = 0;
-    for (int p = 0; p < a.nphase; ++p) gx = gx > a.pmt[p] * a.n_tiles ? gx : a.pmt[p] * a.n_tiles;
-  }
+static void launch_cfg(const ConvFwdArgs& a, int gx, hipStream_t s) {
   dim3 grid(gx, a.nphase > 0 ? a.nphase : 1, a.nslice > 1 ? a.nslice : 1), block(NW * 64);
   const int rs = a.res == nullptr ? 0 : (a.res_phase >= 0 && a.nphase > 0 ? 2 : 1);
   const int epi = a.bnb ? a.bnb + 1 : (a.stats != nullptr ? 1 : 0);
@@ -916,7 +882,7 @@ static void launch_cfg(const ConvFwdArgs& a, hipStream_t s) {
 }
 
 template <int DT>
-static void launch_tile(const ConvFwdArgs& a, int bm, int bn, int bk, hipStream_t s);
+static void launch_tile(const ConvFwdArgs& a, int gx, int bm, int bn, int bk, hipStream_t s);
 
 template <int DT>
 static void launch_dt(ConvFwdArgs a, int bm, int bn, int bk, hipStream_t s) {
@@ -924,47 +890,23 @@ static void launch_dt(ConvFwdArgs a, int bm, int bn, int bk, hipStream_t s) {
   // on the same box in round 5 (ResNet-18 20.33/20.32 -> 20.23/20.23 ms, ResNet-50 73.09/73.19 -> 73.05/73.00 ms
   // with it off); the knob was removed in round 6
   a.stage_out = 0;
-  a.m_tiles = (int)((a.M + bm - 1) / bm);
-  a.n_tiles = a.Kout / bn;
-  {
-    const FastDiv f1 = make_fastdiv((uint32_t)(a.Pm * a.Qm)), f2 = make_fastdiv((uint32_t)a.Qm);
-    a.pq_mul = f1.mul; a.pq_shift = f1.shift; a.q_mul = f2.mul; a.q_shift = f2.shift;
-  }
-  int srows = 0;  // statistics rows: one per (phase, M tile)
-  if (a.nphase > 0) {
-    int any = 0, maxmt = 0;
-    for (int p = 0; p < a.nphase; ++p) {
-      a.pmt[p] = (int)(((int64_t)a.N * a.pPm[p] * a.pQm[p] + bm - 1) / bm);
-      any |= a.pmt[p];
-      maxmt = maxmt > a.pmt[p] ? maxmt : a.pmt[p];
-      if (a.pPm[p] > 0 && a.pQm[p] > 0) {
-        const FastDiv f1 = make_fastdiv((uint32_t)(a.pPm[p] * a.pQm[p])), f2 = make_fastdiv((uint32_t)a.pQm[p]);
-        a.ppq_mul[p] = f1.mul; a.ppq_shift[p] = f1.shift; a.pq1_mul[p] = f2.mul; a.pq1_shift[p] = f2.shift;
-      }
-    }
-    if (!any || a.n_tiles == 0) return;
-    a.srows_pp = maxmt;
-    srows = a.nphase * maxmt;
-  } else if (a.m_tiles * a.n_tiles == 0) {
-    return;
-  } else {
-    a.srows_pp = a.m_tiles;
-    srows = a.m_tiles;
-  }
+  int gx = 0;
+  const int srows = conv_geom_plan(a, bm, bn, &gx);  // statistics rows: one per (phase, M tile)
+  if (gx == 0) return;
   const int KO = a.bnb == 3 ? 4 : 2;
   const int nsl = a.nslice > 1 ? a.nslice : 1;  // slice-batched grouped conv: rows span every slice's channels
   Scratch part(a.stats ? (size_t)srows * a.Kout * nsl * KO * sizeof(float) : 0, s);
   a.srows = part.as<float>();
-  launch_tile<DT>(a, bm, bn, bk, s);
+  launch_tile<DT>(a, gx, bm, bn, bk, s);
   if (a.stats) stat_rows_reduce_launch(a.srows, srows, a.Kout * nsl * KO, a.stats, s, a.stats_ld);
 }
 
 template <int DT>
-static void launch_tile(const ConvFwdArgs& a, int bm, int bn, int bk, hipStream_t s) {
+static void launch_tile(const ConvFwdArgs& a, int gx, int bm, int bn, int bk, hipStream_t s) {
   // LDS ring depth: 2 for BK=64, 3 for BK=32 (round-3/4 sweeps)
 #define PDT_CFGN(BM_, BN_, BK_, WN_, ST_, NW_)            \
   if (bm == BM_ && bn == BN_ && bk == BK_) {               \
-    launch_cfg<DT, BM_, BN_, BK_, WN_, ST_, NW_>(a, s);    \
+    launch_cfg<DT, BM_, BN_, BK_, WN_, ST_, NW_>(a, gx, s); \
     return;                                                \
   }
 #define PDT_CFG(BM_, BN_, BK_, WN_, ST_) PDT_CFGN(BM_, BN_, BK_, WN_, ST_, 4)
@@ -1002,16 +944,16 @@ static void launch_tile(const ConvFwdArgs& a, int bm, int bn, int bk, hipStream_
   // 256 x 128 kernel this replaces ran 750 / 441 on the same shapes.  Outputs are bit-identical to the 128 x 128
   // tile (same K order); the BN statistics differ in the order the per-tile partial rows are summed.
   if (bm == 256 && bn == 128 && (bk == 32 || bk == 64)) {
-    launch_cfg<DT, 256, 128, 32, 2, 3, 4>(a, s);
+    launch_cfg<DT, 256, 128, 32, 2, 3, 4>(a, gx, s);
     return;
   }
   const bool sliced = (a.ldy && a.ldy != a.Kout) || a.cs != a.C;
   if (bk == 64 && bm == 256 && bn == 256 && a.C % 64 == 0 && !sliced) {
-    launch_pp<DT, 256, 256>(a, s);
+    launch_pp<DT, 256, 256>(a, gx, s);
     return;
   }
   if (bk == 64 && bm == 512 && bn == 128 && a.C % 64 == 0 && !sliced) {
-    launch_pp<DT, 512, 128>(a, s);
+    launch_pp<DT, 512, 128>(a, gx, s);
     return;
   }
   PDT_CFGN(256, 256, 32, 4, 4, 8)  // 8 waves (2 x 4 of 128 x 64), 4-stage BK=32 ring (128 KB), 2 steps in flight

@@ -825,25 +825,18 @@ bool conv_l1_eligible(const ConvFwdArgs& a, int* flip) {
     if (!conv_l1_pp_on() || a.res || a.pre_coef || a.nslice > 1 || a.bnb > 1) return false;
     if (a.cs % 8 != 0 || a.ldy % 8 != 0 || a.cs < 64 || a.ldy < 64) return false;
   }
-  if (a.nphase == 0) {
-    if (a.T == 3 && a.U == 3 && a.ist_h == 1 && a.ist_w == 1 && a.ioff_h == -1 && a.ioff_w == -1 &&
-        a.tstep_h == 1 && a.tstep_w == 1 && a.ost_h == 1 && a.ost_w == 1 && a.ooff_h == 0 && a.ooff_w == 0 &&
-        a.Pm == a.H && a.Qm == kW && a.OH == a.H) {
-      *flip = 0;
-      return true;
-    }
+  if (a.nphase > 1) return false;
+  // forward: in = i - 1 + t; single-phase backward-data of a stride-1 3x3 conv: in = i + 1 - t (taps flipped)
+  const bool bwd = a.nphase == 1;
+  const ConvGeom g = bwd ? a.with_phase(0) : ConvGeom(a);
+  const int d = bwd ? -1 : 1;
+  if (g.T != 3 || g.U != 3 || g.ist_h != 1 || g.ist_w != 1 || g.ioff_h != -d || g.ioff_w != -d || g.tstep_h != d ||
+      g.tstep_w != d || g.ost_h != 1 || g.ost_w != 1 || g.ooff_h != 0 || g.ooff_w != 0 || g.Pm != g.H || g.Qm != kW ||
+      g.OH != g.H)
     return false;
-  }
-  // single-phase backward-data of a stride-1 3x3 conv: in = i + 1 - t (taps flipped)
-  if (a.nphase == 1 && a.pT[0] == 3 && a.pU[0] == 3 && a.pioff_h[0] == 1 && a.pioff_w[0] == 1 &&
-      a.tstep_h == -1 && a.tstep_w == -1 && a.ist_h == 1 && a.ist_w == 1 && a.ost_h == 1 && a.ost_w == 1 &&
-      a.pooff_h[0] == 0 && a.pooff_w[0] == 0 && a.pPm[0] == a.H && a.pQm[0] == kW && a.OH == a.H) {
-    *flip = 1;
-    return true;
-  }
-  return false;
+  *flip = bwd ? 1 : 0;
+  return true;
 }
-
 
 int conv_l1_set_pp(int mode) {
   const int old = g_conv_l1_pp;

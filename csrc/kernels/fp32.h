@@ -2,11 +2,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_geom.h"
+
 namespace pdt {
 
-// fp32 implicit-GEMM convolution (same geometry contract as ConvFwdArgs, conv_fwd.hip): forward, multi-phase
-// backward-data, 1x1 / linear layers.  Optional residual add and BN statistics rows.
-struct Conv32Args {
+// fp32 implicit-GEMM convolution (geometry: ConvGeom, the contract of conv_fwd.hip): forward, multi-phase
+// backward-data, 1x1 / linear layers.  Optional residual add and BN statistics rows.  ConvGeom::cs == 4: the stem's
+// "window" mode over a zero-padded NHWC4 image, one 32-element K-step = 8 consecutive pixels x 4 channels of a kernel
+// row (conv_fwd.hip's window mode).
+struct Conv32Args : ConvGeom {
   const float* x;
   const float* w;
   float* y;
@@ -23,21 +27,6 @@ struct Conv32Args {
   // receive 4 quantities per channel: (sum dz, sum dz * xhat1, sum dz, sum dz * xhat2)
   const float* bn_y2 = nullptr;
   const float* bn_coef2 = nullptr;
-  float* srows;
-  int srows_pp;
-  int N, H, W, C, Kout, T, U;
-  int cs;  // elements per input pixel (0: == C).  4: the stem's "window" mode over a zero-padded NHWC4 image, one
-           // 32-element K-step = 8 consecutive pixels x 4 channels of a kernel row (conv_fwd.hip's window mode)
-  int Pm, Qm;
-  int ist_h, ist_w, ioff_h, ioff_w, tstep_h, tstep_w;
-  int OH, OW, ost_h, ost_w, ooff_h, ooff_w;
-  int64_t M;
-  int m_tiles, n_tiles;
-  uint32_t pq_mul, pq_shift, q_mul, q_shift;
-  int nphase;
-  int pT[4], pU[4], pioff_h[4], pioff_w[4], pPm[4], pQm[4], pooff_h[4], pooff_w[4], pmt[4];
-  int64_t pwoff[4];
-  uint32_t ppq_mul[4], ppq_shift[4], pq1_mul[4], pq1_shift[4];
 };
 void conv32_launch(Conv32Args a, int bm, int bn, hipStream_t s);
 // 3x3 / stride-1 same-grid convolutions on 64-channel output tiles: the halo kernel (default) or conv32_kernel (0); returns the

@@ -158,21 +158,9 @@ PDT_DEVICE void conv32_epilogue(const Conv32Args& a, f32x4_t (&acc)[BN / WAVES_N
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool RES>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv32_kernel(Conv32Args args) {
   Conv32Args a = args;
-  if (args.nphase > 0) {  // multi-phase launch (strided backward-data): this block's phase geometry
-    const int ph = blockIdx.y;
-    a.T = args.pT[ph]; a.U = args.pU[ph];
-    a.ioff_h = args.pioff_h[ph]; a.ioff_w = args.pioff_w[ph];
-    a.Pm = args.pPm[ph]; a.Qm = args.pQm[ph];
-    a.ooff_h = args.pooff_h[ph]; a.ooff_w = args.pooff_w[ph];
-    a.m_tiles = args.pmt[ph];
-    a.M = (int64_t)a.N * a.Pm * a.Qm;
-    a.w = args.w + args.pwoff[ph];
-    a.pq_mul = args.ppq_mul[ph]; a.pq_shift = args.ppq_shift[ph];
-    a.q_mul = args.pq1_mul[ph]; a.q_shift = args.pq1_shift[ph];
-    if ((int)blockIdx.x >= a.m_tiles * a.n_tiles) {
-      zero_stat_row32<EPI, BN>(a);
-      return;
-    }
+  if (args.nphase > 0 && !select_phase(a, args, args.w, blockIdx.y)) {  // strided backward-data: this block's phase
+    zero_stat_row32<EPI, BN>(a);
+    return;
   }
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int WN = BN / WAVES_N, WM = BM / WAVES_M;
@@ -460,18 +448,16 @@ int conv32_set_halo(int on) {
   return prev;
 }
 
-static bool conv32_halo_ok(const Conv32Args& a, int bn) {
-  if (!g_conv32_halo || bn != 64 || a.nphase > 1 || a.Kout % 64 != 0 || a.C % 32 != 0) return false;
+static bool conv32_halo_ok(const Conv32Args& args, int bn) {
+  if (!g_conv32_halo || bn != 64 || args.nphase > 1) return false;
+  const ConvGeom a = args.nphase == 1 ? args.with_phase(0) : ConvGeom(args);  // what the (single) phase runs with
+  if (a.Kout % 64 != 0 || a.C % 32 != 0) return false;
   if (a.cs != 0 && a.cs != a.C) return false;
-  const bool ph = a.nphase == 1;
-  const int T = ph ? a.pT[0] : a.T, U = ph ? a.pU[0] : a.U;
-  const int ioh = ph ? a.pioff_h[0] : a.ioff_h, iow = ph ? a.pioff_w[0] : a.ioff_w;
-  const int Pm = ph ? a.pPm[0] : a.Pm, Qm = ph ? a.pQm[0] : a.Qm;
-  if (T != 3 || U != 3 || a.ist_h != 1 || a.ist_w != 1 || Pm != a.H || Qm != a.W) return false;
+  if (a.T != 3 || a.U != 3 || a.ist_h != 1 || a.ist_w != 1 || a.Pm != a.H || a.Qm != a.W) return false;
   if (a.ost_h != 1 || a.ost_w != 1 || a.OH != a.H || a.OW != a.W) return false;
-  if (ph ? (a.pooff_h[0] != 0 || a.pooff_w[0] != 0) : (a.ooff_h != 0 || a.ooff_w != 0)) return false;
+  if (a.ooff_h != 0 || a.ooff_w != 0) return false;
   for (int t = 0; t < 3; ++t) {
-    const int dh = ioh + t * a.tstep_h, dw = iow + t * a.tstep_w;
+    const int dh = a.ioff_h + t * a.tstep_h, dw = a.ioff_w + t * a.tstep_w;
     if (dh < -1 || dh > 1 || dw < -1 || dw > 1) return false;
   }
   if (a.W < 1 || ((a.W + 254) / a.W + 3) * (a.W + 2) > kHalo32Rows) return false;
@@ -481,31 +467,9 @@ static bool conv32_halo_ok(const Conv32Args& a, int bn) {
 void conv32_launch(Conv32Args a, int bm, int bn, hipStream_t s) {
   const bool halo = conv32_halo_ok(a, bn);
   if (halo) bm = 256;
-  a.m_tiles = (int)((a.M + bm - 1) / bm);
-  a.n_tiles = a.Kout / bn;
-  {
-    const FastDiv f1 = make_fastdiv((uint32_t)(a.Pm * a.Qm)), f2 = make_fastdiv((uint32_t)a.Qm);
-    a.pq_mul = f1.mul; a.pq_shift = f1.shift; a.q_mul = f2.mul; a.q_shift = f2.shift;
-  }
-  int srows = 0, gx = a.m_tiles * a.n_tiles;
-  if (a.nphase > 0) {
-    int maxmt = 0;
-    for (int p = 0; p < a.nphase; ++p) {
-      a.pmt[p] = (int)(((int64_t)a.N * a.pPm[p] * a.pQm[p] + bm - 1) / bm);
-      maxmt = maxmt > a.pmt[p] ? maxmt : a.pmt[p];
-      if (a.pPm[p] > 0 && a.pQm[p] > 0) {
-        const FastDiv f1 = make_fastdiv((uint32_t)(a.pPm[p] * a.pQm[p])), f2 = make_fastdiv((uint32_t)a.pQm[p]);
-        a.ppq_mul[p] = f1.mul; a.ppq_shift[p] = f1.shift; a.pq1_mul[p] = f2.mul; a.pq1_shift[p] = f2.shift;
-      }
-    }
-    a.srows_pp = maxmt;
-    srows = a.nphase * maxmt;
-    gx = maxmt * a.n_tiles;
-  } else {
-    a.srows_pp = a.m_tiles;
-    srows = a.m_tiles;
-  }
-  if (gx == 0 || a.n_tiles == 0) return;
+  int gx = 0;
+  const int srows = conv_geom_plan(a, bm, bn, &gx);
+  if (gx == 0) return;
   PDT_COUNT(a.nphase > 0 ? "conv32_dgrad" : "conv32_fwd");
   const int KO = a.bnb && a.bn_y2 ? 4 : 2;
   Scratch part(a.stats ? (size_t)srows * a.Kout * KO * sizeof(float) : 0, s);

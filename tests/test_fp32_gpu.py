@@ -106,6 +106,44 @@ def test_conv32_fwd_dgrad_wgrad_match_torch(shape):
         assert _rel(dw.view(cout, k, k, cin), w.grad.permute(0, 2, 3, 1)) < 1e-5, tile
 
 
+def test_conv32_dgrad_fused_bn_phases_with_unequal_tile_counts():
+    """The fused BN-backward reduce on a multi-phase backward-data launch whose phases have different M-tile counts
+    (3 x 13 x 13, stride 2: 147 / 126 / 126 / 108 rows on 128-row tiles): the grid is sized for the largest phase, so
+    the other phases' surplus blocks must zero the statistics rows they own."""
+    from pytorch_distributed_template_amd.ops import native
+    from pytorch_distributed_template_amd.ops.conv import dgrad_phases, dgrad_weight_index
+    C = native.C
+    N, H, cin, cout, k, st, pad = 3, 13, 128, 64, 3, 2, 1
+    torch.manual_seed(5)
+    w = torch.randn(cout, cin, k, k, device=DEV) / (cin * k * k) ** 0.5
+    P = (H + 2 * pad - k) // st + 1
+    gy = torch.randn(N, cout, P, P, device=DEV)
+    ref = torch.nn.grad.conv2d_input((N, cin, H, H), w, gy, stride=st, padding=pad).permute(0, 2, 3, 1)
+    wflat = w.permute(0, 2, 3, 1).reshape(-1)
+    pieces, phases, off = [], [], 0
+    for ph, pw, rs, ss, ioff_h, ioff_w in dgrad_phases(k, k, st, pad):
+        idx = dgrad_weight_index(cout, cin, k, k, rs, ss).to(DEV)
+        pieces.append(wflat[idx])
+        phases.append([ph, pw, len(rs), len(ss), ioff_h, ioff_w, off])
+        off += idx.numel()
+    y1 = torch.randn(N, H, H, cin, device=DEV)
+    yf = y1.view(-1, cin)
+    mean, invstd = yf.mean(0), torch.rsqrt(yf.var(0, unbiased=False) + 1e-5)
+    scale, shift = torch.rand(cin, device=DEV) + 0.5, torch.randn(cin, device=DEV) * 0.3
+    coef = torch.cat([scale, shift, mean, invstd]).contiguous()
+    act = torch.relu(y1 * scale + shift)  # the stored activation: the mask reference
+    slots = torch.zeros(C.stat_slots() * cin * 2, dtype=torch.float64, device=DEV)
+    dz = torch.empty(N, H, H, cin, device=DEV)
+    C.conv32_dgrad(gy.permute(0, 2, 3, 1).contiguous(), torch.cat(pieces), dz, None, N, P, P, cout, cin, H, H, st,
+                   phases, 128, 64, bn_mref=act, bn_y1=y1, bn_coef=coef, stats=slots)
+    assert _rel(dz, ref * (act > 0)) < 1e-5
+    sums = slots.view(-1, cin, 2).sum(0)
+    dzf = dz.view(-1, cin).double()
+    xhat = ((yf - mean) * invstd).double()
+    assert torch.allclose(sums[:, 0], dzf.sum(0), rtol=1e-6, atol=1e-3)
+    assert torch.allclose(sums[:, 1], (dzf * xhat).sum(0), rtol=1e-6, atol=1e-3)
+
+
 def _setup(arch, N, HW, seed=0):
     from pytorch_distributed_template_amd.models import resnet
     from pytorch_distributed_template_amd.models.executor32 import ResNetExecutor32

@@ -908,6 +908,38 @@ def test_conv_dgrad_fused_bn_bk32_ring_bit_identical(mode, bm, bn):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("N,tile", [(3, (128, 128, 64)), (6, (256, 64, 64))])
+def test_conv_dgrad_fused_bn_phases_with_unequal_tile_counts(N, tile, dtype):
+    """A statistics epilogue on a multi-phase launch whose phases have different M-tile counts (13 x 13, stride 2:
+    N * 49 / 42 / 42 / 36 rows): the grid is sized for the largest phase, so the other phases' surplus blocks must
+    zero the statistics rows they own.  dz against torch, the slot sums against fp64 sums of the kernel's own dz."""
+    from pytorch_distributed_template_amd.ops import conv, native
+    bm, bn, _ = tile
+    H = W = 13
+    C, K, R, st, pad = bn, 192 - bn, 3, 2, 1
+    assert len({-(-N * ((H - ph + 1) // 2) * ((W - pw + 1) // 2) // bm) for ph in (0, 1) for pw in (0, 1)}) > 1
+    torch.manual_seed(19)
+    P, Q = conv.out_hw(H, W, R, R, st, pad)
+    dy = _rand16(N, P, Q, K, dtype=dtype)
+    w = _rand16(K, R, R, C, dtype=dtype, scale=(1.0 / (K * R * R)) ** 0.5)
+    y1 = _rand16(N, H, W, C, dtype=dtype)
+    yf = y1.float().view(-1, C)
+    m1, i1 = yf.mean(0), torch.rsqrt(yf.var(0, unbiased=False) + 1e-5)
+    coef1 = torch.cat([torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV) * 0.3, m1, i1]).contiguous()
+    slots = torch.zeros(native.C.stat_slots() * C * 2, dtype=torch.float64, device=DEV)
+    dz = conv.conv_dgrad(dy, w, H, W, st, pad, bnb=(1, y1, coef1, None, None, None, slots), tile=tile)
+    plain = torch.nn.grad.conv2d_input((N, C, H, W), w.float().permute(0, 3, 1, 2), dy.float().permute(0, 3, 1, 2),
+                                       stride=st, padding=pad).permute(0, 2, 3, 1)
+    mask = (y1.float() * coef1[:C] + coef1[C:2 * C]) > 0
+    assert _rel(dz, plain * mask) < 1e-2
+    sums = slots.view(-1, C, 2).sum(0)
+    dzf = dz.float().view(-1, C).double()
+    x1 = ((yf - m1) * i1).double()
+    assert torch.allclose(sums[:, 0], dzf.sum(0), rtol=1e-6, atol=1e-3)
+    assert torch.allclose(sums[:, 1], (dzf * x1).sum(0), rtol=1e-6, atol=1e-3)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("NHW", [(4, 56, 56), (3, 13, 11)])
 @pytest.mark.parametrize("mode,cin", [(2, 64), (3, 64), (2, 128)])
 def test_conv1x1_c64_dgrad_bnb_matches_generic(dtype, NHW, mode, cin):
