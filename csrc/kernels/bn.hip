@@ -318,6 +318,7 @@ static void bn_apply_dt(const uint16_t* y, const float* coef, const uint16_t* re
   PDT_AP(1, false, false) PDT_AP(2, false, false) PDT_AP(1, true, true) PDT_AP(2, true, true)
 #undef PDT_AP
 #undef PDT_TARGS
+  pdt_hip_fail("bn_apply: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
 }
 
 void bn_apply_launch(int dtype, const uint16_t* y, const float* coef, const uint16_t* res, const float* rcoef,
@@ -432,6 +433,7 @@ void bn_bwd_reduce_launch(int dtype, const uint16_t* g, const uint8_t* out, cons
     PDT_BR(kF16, true, 1) PDT_BR(kF16, true, 2) PDT_BR(kF16, false, 1) PDT_BR(kF16, false, 2)
   }
 #undef PDT_BR
+  pdt_hip_fail("bn_bwd_reduce: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
 }
 
 // -------------------------------------------------------------------------------------------------

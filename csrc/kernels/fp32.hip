@@ -1098,6 +1098,7 @@ void bn_apply32_launch(const float* y, const float* coef, const float* res, cons
   }
   PDT_A32(0, true) PDT_A32(1, true) PDT_A32(2, true) PDT_A32(0, false) PDT_A32(1, false) PDT_A32(2, false)
 #undef PDT_A32
+  pdt_hip_fail("bn_apply32: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
 }
 
 // Backward reduce: dz = g * (mref > 0) (mref: the post-ReLU activation, optional); per branch b:
@@ -1200,6 +1201,7 @@ void bn_bwd_reduce32_launch(const float* g, const float* mref, const float* y1, 
   PDT_R32(true, 1, 1) PDT_R32(true, 2, 1) PDT_R32(false, 1, 1) PDT_R32(false, 2, 1)
   PDT_R32(true, 1, 2) PDT_R32(true, 2, 2) PDT_R32(false, 1, 2) PDT_R32(false, 2, 2)
 #undef PDT_R32
+  pdt_hip_fail("bn_bwd_reduce32: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
 }
 
 // dy_b = A_b*dz + B_b*y_b + C_b, dz = g * (mref > 0); optionally writes dz (identity-branch gradient)
@@ -1243,6 +1245,7 @@ void bn_bwd_apply32_launch(const float* g, const float* mref, const float* y1, c
   PDT_B32(true, 1, false) PDT_B32(true, 1, true) PDT_B32(true, 2, false) PDT_B32(true, 2, true)
   PDT_B32(false, 1, false) PDT_B32(false, 1, true) PDT_B32(false, 2, false) PDT_B32(false, 2, true)
 #undef PDT_B32
+  pdt_hip_fail("bn_bwd_apply32: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
 }
 
 // stem BN + ReLU + MaxPool(3, 2, 1), argmax (0..8) as uint8 (the backward's routing)

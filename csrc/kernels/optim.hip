@@ -99,7 +99,8 @@ void widen16_launch(int dtype, const uint16_t* in, float* out, int64_t n, hipStr
 }
 
 // GradScaler._amp_update_scale_: scale *= backoff on inf (tracker = 0), else tracker += 1 and
-// scale *= growth when tracker reaches the interval (tracker = 0).  Resets found_inf for the next step.
+// scale *= growth when tracker reaches the interval (tracker = 0; a growth that would overflow keeps the scale).
+// found_inf is only read here: DeviceGradScaler.unscale_check clears it before the next step's scan.
 __global__ void amp_update_kernel(float* scale, int* tracker, float* found_inf, float growth, float backoff,
                                   int interval) {
   if (threadIdx.x != 0) return;

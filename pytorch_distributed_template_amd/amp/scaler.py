@@ -64,7 +64,10 @@ class DeviceGradScaler:
             else:
                 self._tracker.add_(1)
                 if int(self._tracker.item()) == self.growth_interval:
-                    self._scale.mul_(self.growth_factor)
+                    # a growth that would overflow fp32 keeps the scale (as the kernel and torch's GradScaler do)
+                    grown = self._scale * self.growth_factor
+                    if bool(torch.isfinite(grown).all()):
+                        self._scale.copy_(grown)
                     self._tracker.zero_()
 
     def state_dict(self) -> dict:
