@@ -22,6 +22,7 @@
 #include "common.h"
 #include "dtypes.h"
 #include "kernels/bn.h"
+#include "kernels/bnact.h"
 #include "kernels/conv1x1.h"
 #include "kernels/conv_fwd.h"
 #include "kernels/conv_l1.h"
@@ -944,6 +945,61 @@ int64_t dwconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, i
   return p.splits;
 }
 
+// ------------------------------------------------------- fused BatchNorm + activation (bnact.hip)
+// x / g / out / dx: NHWC 16-bit viewed as [rows, C]; act: 0 identity, 1 ReLU, 2 ReLU6, 3 Hardswish.
+// The two reduce passes return (row blocks, row lanes per block): a thread's fp32 chain is
+// ceil(rows / (blocks * lanes)) additions long, followed by the fp32 sum over the block's lanes.
+pdt::BnActPlan bnact_geom(const char* op, const Tensor& a, const Tensor* b, const Tensor* c, int64_t rows, int64_t C,
+                          int64_t act, int* dt) {
+  *dt = dt16(a, op);
+  TORCH_CHECK((b == nullptr || dt16(*b, op) == *dt) && (c == nullptr || dt16(*c, op) == *dt), op, ": mixed dtypes");
+  TORCH_CHECK(C > 0 && C % 8 == 0 && C <= pdt::kBnActMaxC, op, ": C must be a multiple of 8 in [8, ", pdt::kBnActMaxC,
+              "], got ", C);
+  TORCH_CHECK(rows > 0 && a.numel() == rows * C && (b == nullptr || b->numel() == rows * C) &&
+                  (c == nullptr || c->numel() == rows * C),
+              op, ": every [rows, C] operand must hold ", rows * C, " elements");
+  TORCH_CHECK(act >= 0 && act <= 3, op, ": act must be 0 (identity), 1 (ReLU), 2 (ReLU6) or 3 (Hardswish), got ", act);
+  return pdt::bnact_plan(rows, (int)C);
+}
+
+std::vector<int64_t> bnact_stats(const Tensor& x, Tensor& slots, int64_t rows, int64_t C) {
+  int dt;
+  const pdt::BnActPlan p = bnact_geom("bnact_stats", x, nullptr, nullptr, rows, C, 0, &dt);
+  TORCH_CHECK(slots.numel() >= pdt::kStatSlots * C * 2, "bnact_stats: slots too small");
+  pdt::bnact_stats_launch(dt, p16(x, "x"), pd(slots, "slots"), rows, (int)C, p, cur_stream());
+  launched("bnact_stats");
+  return {p.blocks, p.rpi};
+}
+
+void bnact_fwd(const Tensor& x, const Tensor& coef, Tensor& out, int64_t rows, int64_t C, int64_t act) {
+  int dt;
+  const pdt::BnActPlan p = bnact_geom("bnact_fwd", x, &out, nullptr, rows, C, act, &dt);
+  TORCH_CHECK(coef.numel() >= 4 * C, "bnact_fwd: coef too small");
+  pdt::bnact_fwd_launch(dt, (int)act, p16(x, "x"), pf(coef, "coef"), p16(out, "out"), rows, (int)C, p, cur_stream());
+  launched("bnact_fwd");
+}
+
+std::vector<int64_t> bnact_bwd_reduce(const Tensor& g, const Tensor& x, const Tensor& coef, Tensor& slots, int64_t rows,
+                                      int64_t C, int64_t act) {
+  int dt;
+  const pdt::BnActPlan p = bnact_geom("bnact_bwd_reduce", g, &x, nullptr, rows, C, act, &dt);
+  TORCH_CHECK(coef.numel() >= 4 * C && slots.numel() >= pdt::kStatSlots * C * 2, "bnact_bwd_reduce: coef / slots too small");
+  pdt::bnact_bwd_reduce_launch(dt, (int)act, p16(g, "g"), p16(x, "x"), pf(coef, "coef"), pd(slots, "slots"), rows, (int)C,
+                               p, cur_stream());
+  launched("bnact_bwd_reduce");
+  return {p.blocks, p.rpi};
+}
+
+void bnact_bwd_apply(const Tensor& g, const Tensor& x, const Tensor& coef, const Tensor& bcoef, Tensor& dx, int64_t rows,
+                     int64_t C, int64_t act) {
+  int dt;
+  const pdt::BnActPlan p = bnact_geom("bnact_bwd_apply", g, &x, &dx, rows, C, act, &dt);
+  TORCH_CHECK(coef.numel() >= 4 * C && bcoef.numel() >= 3 * C, "bnact_bwd_apply: coef / bcoef too small");
+  pdt::bnact_bwd_apply_launch(dt, (int)act, p16(g, "g"), p16(x, "x"), pf(coef, "coef"), pf(bcoef, "bcoef"), p16(dx, "dx"),
+                              rows, (int)C, p, cur_stream());
+  launched("bnact_bwd_apply");
+}
+
 // ---------------------------------------------------------------------------- VGG family (vgg.hip)
 // out = MaxPool(2, 2)(relu(y * coef[0:C] + coef[C:2C])), idx = window argmax (0..3) per pooled element (training)
 void bn_relu_maxpool2(const Tensor& y, const Tensor& coef, Tensor& out, const OptT& idx, int64_t N, int64_t H,
@@ -1560,6 +1616,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_pool_bwd_reduce", &stem_pool_bwd_reduce);
   m.def("stem_pool_bwd_reduce_out", &stem_pool_bwd_reduce_out);
   m.def("stem_pool_bwd_apply", &stem_pool_bwd_apply);
+  m.def("bnact_stats", &bnact_stats, py::arg("x"), py::arg("slots"), py::arg("rows"), py::arg("C"));
+  m.def("bnact_fwd", &bnact_fwd, py::arg("x"), py::arg("coef"), py::arg("out"), py::arg("rows"), py::arg("C"),
+        py::arg("act"));
+  m.def("bnact_bwd_reduce", &bnact_bwd_reduce, py::arg("g"), py::arg("x"), py::arg("coef"), py::arg("slots"),
+        py::arg("rows"), py::arg("C"), py::arg("act"));
+  m.def("bnact_bwd_apply", &bnact_bwd_apply, py::arg("g"), py::arg("x"), py::arg("coef"), py::arg("bcoef"),
+        py::arg("dx"), py::arg("rows"), py::arg("C"), py::arg("act"));
   m.def("dwconv_fwd", &dwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("N"), py::arg("H"), py::arg("W"),
         py::arg("C"), py::arg("R"), py::arg("stride"));
   m.def("dwconv_dgrad", &dwconv_dgrad, py::arg("dy"), py::arg("w"), py::arg("dx"), py::arg("N"), py::arg("H"),

@@ -159,6 +159,12 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
                    help="torch engine: run qualifying depthwise convs (3x3 / 5x5, stride 1 / 2, no bias, channels % 8 "
                         "== 0) on the native HIP depthwise kernels where the activations are 16-bit channels_last "
                         "GPU tensors; elsewhere (CPU, fp32, validation) the modules fall back to F.conv2d")
+    g.add_argument("--native-bnact", default="off", choices=["off", "on"],
+                   help="torch engine: run qualifying BatchNorm2d layers (affine, running statistics, channels % 8 == 0, "
+                        "<= 2048) fused with the ReLU / ReLU6 / Hardswish that follows them on the native HIP kernels "
+                        "where the training activations are 16-bit channels_last GPU tensors; elsewhere (CPU, fp32, "
+                        "validation) the modules fall back to the stock ops; ignored when --sync_batchnorm converts "
+                        "the model")
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

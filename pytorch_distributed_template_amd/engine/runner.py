@@ -340,6 +340,16 @@ def main(mode: str, argv: Optional[list] = None) -> int:
         from ..ops.depthwise import convert_depthwise
         ddp_print("=> native depthwise: {} conv(s) of {} converted".format(convert_depthwise(model), args.arch),
                   logger, rank)
+    if getattr(args, "native_bnact", "off") == "on" and engine == "torch":
+        if distributed and bool(getattr(args, "sync_batchnorm", False)):
+            # the trainer's condition for SyncBatchNorm.convert_sync_batchnorm, which rebuilds every _BatchNorm
+            # and would drop the absorbed activations
+            ddp_print("=> native bnact: ignored, --sync_batchnorm converts the model's BatchNorms", logger, rank)
+        else:
+            from ..ops.bnact import convert_bnact
+            n_bn, n_absorbed = convert_bnact(model)
+            ddp_print("=> native bnact: {} BatchNorm(s) of {} converted, {} activation(s) fused".format(
+                n_bn, args.arch, n_absorbed), logger, rank)
     trainer = build_trainer(mode, model, args, device, dtype, engine, world)
     optimizer = trainer.optimizer
     gn = getattr(args, "gpu_normalize", "off")

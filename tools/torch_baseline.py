@@ -17,6 +17,9 @@ p.add_argument("--benchmark", type=int, default=1, help="cudnn.benchmark (MIOpen
 p.add_argument("--cl", type=int, default=1)
 p.add_argument("--native-depthwise", default="off", choices=["off", "on"],
                help="on: qualifying depthwise convs run on the native HIP kernels (ops/depthwise.py); off: MIOpen")
+p.add_argument("--native-bnact", default="off", choices=["off", "on"],
+               help="on: qualifying BatchNorm2d (+ ReLU / ReLU6 / Hardswish) layers run on the native fused HIP kernels "
+                    "(ops/bnact.py); off: MIOpen batch norm + a separate activation")
 a = p.parse_args()
 torch.backends.cudnn.benchmark = bool(a.benchmark)
 import threading
@@ -36,6 +39,11 @@ if a.native_depthwise == "on":
     from pytorch_distributed_template_amd.ops.depthwise import convert_depthwise
     n_dw = convert_depthwise(m)
     print(f"native depthwise: {n_dw} conv(s) converted", flush=True)
+n_bn = n_act = 0
+if a.native_bnact == "on":
+    from pytorch_distributed_template_amd.ops.bnact import convert_bnact
+    n_bn, n_act = convert_bnact(m)
+    print(f"native bnact: {n_bn} BatchNorm(s) converted, {n_act} activation(s) fused", flush=True)
 if a.cl:
     m = m.to(memory_format=torch.channels_last)
 opt = torch.optim.SGD(m.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4)
@@ -65,5 +73,6 @@ for _ in range(a.steps):
 print()
 el = (time.time() - t) / a.steps
 print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl,
-                  "native_depthwise": a.native_depthwise, "depthwise_converted": n_dw, "ms_per_step": el * 1e3,
+                  "native_depthwise": a.native_depthwise, "depthwise_converted": n_dw,
+                  "native_bnact": a.native_bnact, "bnact_converted": n_bn, "bnact_fused": n_act, "ms_per_step": el * 1e3,
                   "img_per_s": a.bs / el, "max_mem_GB": torch.cuda.max_memory_allocated() / 1e9}))
