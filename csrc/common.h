@@ -25,6 +25,13 @@ inline FastDiv make_fastdiv(uint32_t d) {
   return FastDiv{(uint32_t)m, s};
 }
 
+// grid of a grid-stride elementwise kernel: one 256-thread block per 256 items, at most `cap` blocks
+inline int ew_blocks(int64_t n, int cap) {
+  int64_t b = (n + 255) / 256;
+  if (b > cap) b = cap;
+  return (int)(b < 1 ? 1 : b);
+}
+
 }  // namespace pdt
 
 // ---- device code: the kernels only (the host C++ compiler of the bindings sees the host half of this header)
@@ -140,6 +147,8 @@ PDT_DEVICE void st16(void* p, uint4 v) {
     *(uint4*)p = v;
   }
 }
+// which form a pass over `bytes`-sized operands takes: non-temporal from 64 MiB on (round-4 sweep)
+inline bool ew_nt(int64_t bytes) { return bytes >= (64ll << 20); }
 
 // Inclusive scan over each 16-lane DPP row (row_shr 1, 2, 4, 8 with zero fill): lane 15 of every row
 // ends with the sum of the row's 16 values.  Pure VALU (no LDS permute traffic).

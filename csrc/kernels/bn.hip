@@ -11,7 +11,7 @@
 #include <cstdlib>
 #include "../common.h"
 #include "bn.h"
-#include "conv_fwd.h"
+#include "col_reduce.h"
 
 namespace pdt {
 
@@ -278,13 +278,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
 // 6.2-6.7 TB/s (two-branch backward 7.3-7.6), U = 8 a few % below 4.  Streams larger than the L2s and MALL use
 // nontemporal loads/stores.
 constexpr int kEwU = 4;
-static int ew_blocks(int64_t n8, int U) {
+static int stream_blocks(int64_t n8, int U) {  // uncapped, unlike common.h's ew_blocks(n, cap) of the looping grids
   const int64_t b = (n8 + 256 * U - 1) / (256 * U);
   if (b >= (int64_t(1) << 31)) pdt_hip_fail("elementwise pass: tensor too large", hipErrorInvalidValue, __FILE__, __LINE__);
   return (int)(b < 1 ? 1 : b);
-}
-static bool ew_nt(int64_t bytes) {
-  return bytes >= (64ll << 20);  // non-temporal loads / stores from 64 MiB operands on (round-4 sweep)
 }
 static bool ew_ch(int C) { return C > 0 && C <= 2048 && (C & (C - 1)) == 0 && C % 8 == 0; }
 
@@ -306,7 +303,7 @@ template <int DT>
 static void bn_apply_dt(const uint16_t* y, const float* coef, const uint16_t* res, const float* rcoef, uint16_t* out,
                         uint8_t* mask, int64_t n, int C, int resmode, bool relu, hipStream_t s) {
   const int64_t n8 = n / 8;
-  auto grid = [&](int U) { return ew_blocks(n8, U); };
+  auto grid = [&](int U) { return stream_blocks(n8, U); };
   const bool wm = mask != nullptr, nt = ew_nt(n * 2), ch = ew_ch(C);
 #define PDT_AP(RM, RL, WM)                                                                                       \
   if (resmode == RM && relu == RL && wm == WM) {                                                                 \
@@ -332,7 +329,7 @@ void bn_apply_launch(int dtype, const uint16_t* y, const float* coef, const uint
 // -------------------------------------------------------------------------------------------------
 // Backward reduce.  dz = g * mask (ReLU bitmask of the block output, optional).  For branch b in {1,2}:
 //   part[blk][c][2b-2] += dz ; part[blk][c][2b-1] += dz * (y_b - mean_b) * invstd_b
-// Each thread owns 8 consecutive channels of a row; rows are strided over the grid.
+// Each thread owns 8 consecutive channels of a row; rows are strided over the grid (col_reduce.h, one column chunk).
 template <int DT, bool MASK, int NBR>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __restrict__ g,
                                                             const uint8_t* __restrict__ mask,
@@ -340,13 +337,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __re
                                                             const float* __restrict__ coef1,
                                                             const uint16_t* __restrict__ y2,
                                                             const float* __restrict__ coef2,
-                                                            float* __restrict__ srows, int64_t rows, int C) {
+                                                            float* __restrict__ srows, int64_t rows, int C,
+                                                            int cvb, int rpi) {
   using E = E16<DT>;
-  const int vpr = C / 8;              // 16-byte vectors per row
-  const int rpi = 256 / vpr;          // rows per block iteration (C <= 2048)
-  const int cv = threadIdx.x % vpr;   // vector (channel group) index
-  const int rl = threadIdx.x / vpr;   // row lane
-  const int c0 = cv * 8;
+  extern __shared__ float red[];  // [rpi][C][NBR * 2]
+  const ColLane ln = col_lanes<8>(C, cvb, rpi);
+  const int c0 = ln.c0;
   float s[NBR * 2][8];
 #pragma unroll
   for (int k = 0; k < NBR * 2; ++k)
@@ -359,81 +355,56 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __re
     i1[e] = coef1[3 * C + c0 + e];
     if constexpr (NBR == 2) { m2[e] = coef2[2 * C + c0 + e]; i2[e] = coef2[3 * C + c0 + e]; }
   }
-  if (rl < rpi) {
-    for (int64_t r = (int64_t)blockIdx.x * rpi + rl; r < rows; r += (int64_t)gridDim.x * rpi) {
+  if (ln.active) {
+    for (int64_t r = (int64_t)blockIdx.x * rpi + ln.rl; r < rows; r += (int64_t)gridDim.x * rpi) {
       const int64_t off = r * C + c0;
-      const uint4 gv = *(const uint4*)(g + off);
-      const uint32_t gw[4] = {gv.x, gv.y, gv.z, gv.w};
+      uint16_t gh[8], y1h[8], y2h[8];
+      unpack8(*(const uint4*)(g + off), gh);
       uint32_t mb = 0xffu;
       if constexpr (MASK) mb = mask[off >> 3];
-      const uint4 y1v = *(const uint4*)(y1 + off);
-      const uint32_t y1w[4] = {y1v.x, y1v.y, y1v.z, y1v.w};
-      uint32_t y2w[4] = {0, 0, 0, 0};
-      if constexpr (NBR == 2) { const uint4 y2v = *(const uint4*)(y2 + off); y2w[0] = y2v.x; y2w[1] = y2v.y; y2w[2] = y2v.z; y2w[3] = y2v.w; }
+      unpack8(*(const uint4*)(y1 + off), y1h);
+      if constexpr (NBR == 2) unpack8(*(const uint4*)(y2 + off), y2h);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const int sh = 16 * (e & 1);
-        float dz = E::to_f((uint16_t)(gw[e >> 1] >> sh));
+        float dz = E::to_f(gh[e]);
         if constexpr (MASK) dz = (mb >> e) & 1u ? dz : 0.f;
-        const float x1 = (E::to_f((uint16_t)(y1w[e >> 1] >> sh)) - m1[e]) * i1[e];
+        const float x1 = (E::to_f(y1h[e]) - m1[e]) * i1[e];
         s[0][e] += dz;
         s[1][e] += dz * x1;
         if constexpr (NBR == 2) {
-          const float x2 = (E::to_f((uint16_t)(y2w[e >> 1] >> sh)) - m2[e]) * i2[e];
+          const float x2 = (E::to_f(y2h[e]) - m2[e]) * i2[e];
           s[2][e] += dz;
           s[3][e] += dz * x2;
         }
       }
     }
   }
-  // block reduction over row lanes: LDS [rpi][C][NBR*2]
-  extern __shared__ float red[];
-  const int K = NBR * 2;
-  if (rl < rpi) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-#pragma unroll
-      for (int k = 0; k < NBR * 2; ++k) red[((int64_t)rl * C + c0 + e) * K + k] = s[k][e];
-  }
-  __syncthreads();
-  float* dst = srows + (int64_t)blockIdx.x * C * K;  // this block's own partial row
-  for (int idx = threadIdx.x; idx < C * K; idx += 256) {
-    float t = 0.f;
-    for (int r = 0; r < rpi; ++r) t += red[(int64_t)r * C * K + idx];
-    dst[idx] = t;
-  }
+  block_rows_out<NBR * 2>(s, ln, red, srows, C, cvb, rpi);
 }
 
-int bn_bwd_reduce_blocks(int64_t rows, int C) {
-  const int rpi = 256 / (C / 8);
-  int64_t b = (rows + rpi * 16 - 1) / (rpi * 16);  // >= 16 rows per thread
-  if (b > 1024) b = 1024;
-  return (int)(b < 1 ? 1 : b);
-}
+// >= 16 rows per thread, at most 1024 blocks
+static ColPlan bn_bwd_reduce_plan(int64_t rows, int C, int K) { return col_plan(rows, C, 8, K, 16, 1024); }
+
+int bn_bwd_reduce_blocks(int64_t rows, int C) { return bn_bwd_reduce_plan(rows, C, 2).blocks; }
 
 void bn_bwd_reduce_launch(int dtype, const uint16_t* g, const uint8_t* out, const uint16_t* y1, const float* coef1,
                           const uint16_t* y2, const float* coef2, double* slots, int blocks, int64_t rows, int C,
                           hipStream_t s) {
-  const int rpi = 256 / (C / 8);
   const int nbr = y2 ? 2 : 1;
-  Scratch part((size_t)blocks * C * nbr * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
-  const size_t smem = (size_t)rpi * C * nbr * 2 * sizeof(float);
+  const ColPlan p = bn_bwd_reduce_plan(rows, C, nbr * 2);
   const bool mask = out != nullptr;
-#define PDT_BR(DT_, M_, NB_)                                                                              \
-  if (mask == M_ && nbr == NB_) {                                                                         \
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<DT_, M_, NB_>), dim3(blocks), dim3(256), smem, s, g, out, y1, \
-                       coef1, y2, coef2, srows, rows, C);                                                  \
-    stat_rows_reduce_launch(srows, blocks, C * nbr * 2, slots, s);                                        \
-    return;                                                                                               \
+  col_reduce_run(blocks, C, nbr * 2, slots, s, [&](float* srows) {
+#define PDT_BR(DT_, M_, NB_)                                                                               \
+  if (dtype == DT_ && mask == M_ && nbr == NB_) {                                                          \
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<DT_, M_, NB_>), dim3(blocks), dim3(256), p.lds, s, g, out, y1, \
+                       coef1, y2, coef2, srows, rows, C, p.cvb, p.rpi);                                    \
+    return;                                                                                                \
   }
-  if (dtype == kBF16) {
     PDT_BR(kBF16, true, 1) PDT_BR(kBF16, true, 2) PDT_BR(kBF16, false, 1) PDT_BR(kBF16, false, 2)
-  } else {
     PDT_BR(kF16, true, 1) PDT_BR(kF16, true, 2) PDT_BR(kF16, false, 1) PDT_BR(kF16, false, 2)
-  }
 #undef PDT_BR
-  pdt_hip_fail("bn_bwd_reduce: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
+    pdt_hip_fail("bn_bwd_reduce: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
+  });
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -578,7 +549,7 @@ void bn_bwd_apply_launch(int dtype, const uint16_t* g, const uint8_t* out, const
                          uint16_t* dy1, const uint16_t* y2, const float* b2, uint16_t* dy2, uint16_t* dz_out, int64_t n,
                          int C, hipStream_t s) {
   const int64_t n8 = n / 8;
-  auto grid = [&](int U) { return ew_blocks(n8, U); };
+  auto grid = [&](int U) { return stream_blocks(n8, U); };
   const bool mask = out != nullptr, wdz = dz_out != nullptr, nt = ew_nt(n * 2), ch = ew_ch(C);
   const int nbr = y2 ? 2 : 1;
 #define PDT_TARGS(...) __VA_ARGS__

@@ -2,6 +2,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "col_reduce.h"
+
 namespace pdt {
 // activation fused behind the BatchNorm (torch's breakpoint conventions, see bnact.hip)
 enum BnAct : int { kActIdentity = 0, kActRelu = 1, kActRelu6 = 2, kActHardswish = 3 };
@@ -10,9 +12,8 @@ constexpr int kBnActMaxC = 2048;
 
 // How a [rows, C] tensor is spread over 256-thread blocks: a block owns `cvb` consecutive 8-channel groups
 // (`chunks` such column chunks cover a row) and `rpi` row lanes; the two reduce kernels run `blocks` row blocks.
-struct BnActPlan {
-  int cvb, rpi, chunks, blocks;
-};
+// col_plan (col_reduce.h) with the cvb that idles the fewest lanes.
+using BnActPlan = ColPlan;
 BnActPlan bnact_plan(int64_t rows, int C);
 
 void bnact_stats_launch(int dtype, const uint16_t* x, double* slots, int64_t rows, int C, const BnActPlan& p,

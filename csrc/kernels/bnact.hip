@@ -14,11 +14,12 @@
 // 256-thread block is cvb channel groups x rpi row lanes; a row of C / 8 groups is split into `chunks` column
 // chunks of cvb groups (grid.y).  bnact_plan picks cvb so that few lanes idle for widths that do not divide 256:
 // C = 1280 (160 groups) runs as 5 chunks of 32 groups x 8 row lanes, C = 24 as 3 groups x 85 row lanes.
-// Statistics are deterministic (no atomics): per-thread fp32 chains, a fixed-order LDS sum over the block's row
-// lanes, one partial row per row block, then stat_rows_reduce into the kStatSlots fp64 slots (conv_fwd.h).
+// The lanes and the deterministic statistics (per-thread fp32 chains, fixed-order LDS sum over the block's row
+// lanes, one partial row per row block, stat_rows_reduce into the fp64 slots) are col_reduce.h's, shared with
+// the BN-backward and pooled reduces.
 #include "../common.h"
 #include "bnact.h"
-#include "conv_fwd.h"
+#include "col_reduce.h"
 
 namespace pdt {
 
@@ -26,7 +27,7 @@ BnActPlan bnact_plan(int64_t rows, int C) {
   const int vpr = C / 8;
   // candidates: at least 8 groups (128 contiguous bytes per row segment) unless the whole row is narrower
   const int lo = vpr < 8 ? vpr : 8, hi = vpr < 256 ? vpr : 256;
-  BnActPlan best{hi, 256 / hi, (vpr + hi - 1) / hi, 1};
+  int best = hi;
   int64_t best_num = -1, best_den = 1;
   for (int cvb = lo; cvb <= hi; ++cvb) {
     const int rpi = 256 / cvb, chunks = (vpr + cvb - 1) / cvb;
@@ -35,15 +36,12 @@ BnActPlan bnact_plan(int64_t rows, int C) {
     if (best_num < 0 || num * best_den >= best_num * den) {
       best_num = num;
       best_den = den;
-      best = BnActPlan{cvb, rpi, chunks, 1};
+      best = cvb;
     }
   }
   // reduce kernels: >= 16 rows per thread, at most 2048 blocks in all
-  int64_t b = (rows + (int64_t)best.rpi * 16 - 1) / ((int64_t)best.rpi * 16);
-  const int64_t cap = 2048 / best.chunks > 0 ? 2048 / best.chunks : 1;
-  if (b > cap) b = cap;
-  best.blocks = (int)(b < 1 ? 1 : b);
-  return best;
+  const int chunks = (vpr + best - 1) / best;
+  return col_plan(rows, C, 8, 2, 16, 2048 / chunks > 0 ? 2048 / chunks : 1, best);
 }
 
 namespace {
@@ -80,45 +78,13 @@ PDT_DEVICE float act_bwd(float u, float g) {
   return g;
 }
 
-struct Lane {
-  int c0, rl;
-  bool active;
-};
-PDT_DEVICE Lane lane_of(int C, int cvb, int rpi) {
-  const int cl = threadIdx.x % cvb, rl = threadIdx.x / cvb;
-  const int cv = blockIdx.y * cvb + cl;
-  return Lane{cv * 8, rl, rl < rpi && cv * 8 < C};
-}
-
-// Block reduction over the row lanes and the block's partial row.  red: [rpi][cvb * 8][K] floats (<= 16 KiB).
-template <int K>
-PDT_DEVICE void block_rows_out(const float (&s)[K][8], const Lane& ln, float* __restrict__ red,
-                               float* __restrict__ srows, int C, int cvb, int rpi) {
-  if (ln.active) {
-    const int base = (ln.rl * cvb + threadIdx.x % cvb) * 8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-#pragma unroll
-      for (int k = 0; k < K; ++k) red[(base + e) * K + k] = s[k][e];
-  }
-  __syncthreads();
-  const int per = cvb * 8 * K;                   // entries of this chunk's part of the partial row
-  const int col0 = blockIdx.y * per;             // its first column of the [C * K] row
-  float* dst = srows + (int64_t)blockIdx.x * C * K;
-  for (int idx = threadIdx.x; idx < per && col0 + idx < C * K; idx += 256) {
-    float t = 0.f;
-    for (int r = 0; r < rpi; ++r) t += red[r * per + idx];
-    dst[col0 + idx] = t;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------- statistics
 template <int DT, bool NT>
 __global__ __launch_bounds__(256) void bnact_stats_kernel(const uint16_t* __restrict__ x, float* __restrict__ srows,
                                                           int64_t rows, int C, int cvb, int rpi) {
   using E = E16<DT>;
   __shared__ float red[256 * 8 * 2];
-  const Lane ln = lane_of(C, cvb, rpi);
+  const ColLane ln = col_lanes<8>(C, cvb, rpi);
   float s[2][8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) s[0][e] = s[1][e] = 0.f;
@@ -152,7 +118,7 @@ __global__ __launch_bounds__(256) void bnact_fwd_kernel(const uint16_t* __restri
                                                         uint16_t* __restrict__ out, int64_t rows, int C, int cvb,
                                                         int rpi) {
   using E = E16<DT>;
-  const Lane ln = lane_of(C, cvb, rpi);
+  const ColLane ln = col_lanes<8>(C, cvb, rpi);
   if (!ln.active) return;
   const int64_t r0 = (int64_t)blockIdx.x * (kU * rpi) + ln.rl;
   uint4 v[kU];
@@ -186,7 +152,7 @@ __global__ __launch_bounds__(256) void bnact_bwd_reduce_kernel(const uint16_t* _
                                                                int rpi) {
   using E = E16<DT>;
   __shared__ float red[256 * 8 * 2];
-  const Lane ln = lane_of(C, cvb, rpi);
+  const ColLane ln = col_lanes<8>(C, cvb, rpi);
   float s[2][8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) s[0][e] = s[1][e] = 0.f;
@@ -236,7 +202,7 @@ __global__ __launch_bounds__(256) void bnact_bwd_apply_kernel(const uint16_t* __
                                                               uint16_t* __restrict__ dx, int64_t rows, int C, int cvb,
                                                               int rpi) {
   using E = E16<DT>;
-  const Lane ln = lane_of(C, cvb, rpi);
+  const ColLane ln = col_lanes<8>(C, cvb, rpi);
   if (!ln.active) return;
   const int64_t r0 = (int64_t)blockIdx.x * (kU * rpi) + ln.rl;
   uint4 gv[kU], xv[kU];
@@ -274,8 +240,6 @@ __global__ __launch_bounds__(256) void bnact_bwd_apply_kernel(const uint16_t* __
   }
 }
 
-bool ew_nt(int64_t bytes) { return bytes >= (64ll << 20); }  // as bn.hip: non-temporal from 64 MiB operands on
-
 dim3 ew_grid(int64_t rows, const BnActPlan& p) {
   const int64_t per = (int64_t)kU * p.rpi, b = (rows + per - 1) / per;
   if (b >= (int64_t(1) << 31)) pdt_hip_fail("bnact: tensor too large", hipErrorInvalidValue, __FILE__, __LINE__);
@@ -305,19 +269,18 @@ dim3 ew_grid(int64_t rows, const BnActPlan& p) {
 void bnact_stats_launch(int dtype, const uint16_t* x, double* slots, int64_t rows, int C, const BnActPlan& p,
                         hipStream_t s) {
   PDT_COUNT("bnact_stats");
-  Scratch part((size_t)p.blocks * C * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
   const bool nt = ew_nt(rows * C * 2);
   const dim3 grid(p.blocks, p.chunks);
+  col_reduce_run(p.blocks, C, 2, slots, s, [&](float* srows) {
 #define PDT_ST(DT_, NT_)                                                                                 \
   if (dtype == DT_ && nt == NT_) {                                                                       \
     hipLaunchKernelGGL((bnact_stats_kernel<DT_, NT_>), grid, dim3(256), 0, s, x, srows, rows, C, p.cvb, p.rpi); \
-    stat_rows_reduce_launch(srows, p.blocks, C * 2, slots, s);                                           \
     return;                                                                                              \
   }
-  PDT_ST(kBF16, false) PDT_ST(kBF16, true) PDT_ST(kF16, false) PDT_ST(kF16, true)
+    PDT_ST(kBF16, false) PDT_ST(kBF16, true) PDT_ST(kF16, false) PDT_ST(kF16, true)
 #undef PDT_ST
-  pdt_hip_fail("bnact_stats: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
+    pdt_hip_fail("bnact_stats: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
+  });
 }
 
 void bnact_fwd_launch(int dtype, int act, const uint16_t* x, const float* coef, uint16_t* out, int64_t rows, int C,
@@ -332,13 +295,12 @@ void bnact_fwd_launch(int dtype, int act, const uint16_t* x, const float* coef, 
 void bnact_bwd_reduce_launch(int dtype, int act, const uint16_t* g, const uint16_t* x, const float* coef, double* slots,
                              int64_t rows, int C, const BnActPlan& p, hipStream_t s) {
   PDT_COUNT("bnact_bwd_reduce");
-  Scratch part((size_t)p.blocks * C * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
   const bool nt = ew_nt(rows * C * 2);
   const dim3 grid(p.blocks, p.chunks);
-  PDT_BNACT_DISPATCH(bnact_bwd_reduce_kernel, grid, g, x, coef, srows, rows, C, p.cvb, p.rpi)
-  if (!launched_) pdt_hip_fail("bnact_bwd_reduce: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
-  stat_rows_reduce_launch(srows, p.blocks, C * 2, slots, s);
+  col_reduce_run(p.blocks, C, 2, slots, s, [&](float* srows) {
+    PDT_BNACT_DISPATCH(bnact_bwd_reduce_kernel, grid, g, x, coef, srows, rows, C, p.cvb, p.rpi)
+    if (!launched_) pdt_hip_fail("bnact_bwd_reduce: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
+  });
 }
 
 void bnact_bwd_apply_launch(int dtype, int act, const uint16_t* g, const uint16_t* x, const float* coef,

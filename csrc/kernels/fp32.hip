@@ -19,7 +19,7 @@
 #include <cstdlib>
 
 #include "../common.h"
-#include "conv_fwd.h"
+#include "col_reduce.h"
 #include "fp32.h"
 
 namespace pdt {
@@ -28,11 +28,7 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 PDT_DEVICE f32x4_t mfma4(float a, float b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
-static int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 16384) b = 16384;
-  return (int)(b < 1 ? 1 : b);
-}
+constexpr int kEwCap = 16384;  // most blocks of a grid-stride elementwise kernel here
 
 // ------------------------------------------------------------------------------------------------ conv32
 template <int EPI, int BN_>
@@ -1090,7 +1086,7 @@ __global__ __launch_bounds__(256) void bn_apply32_kernel(const float* __restrict
 void bn_apply32_launch(const float* y, const float* coef, const float* res, const float* rcoef, float* out, int64_t n,
                        int C, int resmode, bool relu, hipStream_t s) {
   const int64_t n4 = n / 4;
-  dim3 g(ew_blocks(n4)), b(256);
+  dim3 g(ew_blocks(n4, kEwCap)), b(256);
 #define PDT_A32(RM, RL)                                                                                          \
   if (resmode == RM && relu == RL) {                                                                             \
     hipLaunchKernelGGL((bn_apply32_kernel<RM, RL>), g, b, 0, s, y, coef, res, rcoef, out, n4, C);                 \
@@ -1108,11 +1104,10 @@ template <bool MASK, int NBR, int NV>
 __global__ __launch_bounds__(256) void bn_bwd_reduce32_kernel(const float* __restrict__ g, const float* __restrict__ mref,
                                                               const float* __restrict__ y1, const float* __restrict__ coef1,
                                                               const float* __restrict__ y2, const float* __restrict__ coef2,
-                                                              float* __restrict__ srows, int64_t rows, int C) {
-  const int vpr = C / 4;
-  const int lanes_c = vpr / NV;              // threads per row
-  const int rpi = 256 / lanes_c;             // rows per block iteration
-  const int cl = threadIdx.x % lanes_c, rl = threadIdx.x / lanes_c;
+                                                              float* __restrict__ srows, int64_t rows, int C,
+                                                              int lanes_c, int rpi) {  // lanes_c: threads per row
+  extern __shared__ float red[];  // [rpi][C][K]
+  const ColLane ln = col_lanes<4>(C, lanes_c, rpi);
   constexpr int K = NBR * 2;
   float s[NV][K][4];
 #pragma unroll
@@ -1121,11 +1116,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce32_kernel(const float* __res
     for (int k = 0; k < K; ++k)
 #pragma unroll
       for (int e = 0; e < 4; ++e) s[q][k][e] = 0.f;
-  if (rl < rpi) {
-    for (int64_t r = (int64_t)blockIdx.x * rpi + rl; r < rows; r += (int64_t)gridDim.x * rpi) {
+  if (ln.active) {
+    for (int64_t r = (int64_t)blockIdx.x * rpi + ln.rl; r < rows; r += (int64_t)gridDim.x * rpi) {
 #pragma unroll
       for (int q = 0; q < NV; ++q) {
-        const int c0 = (cl + q * lanes_c) * 4;
+        const int c0 = ln.c0 + q * lanes_c * 4;
         const int64_t off = r * C + c0;
         f32x4v dz = *(const f32x4v*)(g + off);
         if constexpr (MASK) {
@@ -1152,56 +1147,36 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce32_kernel(const float* __res
       }
     }
   }
-  extern __shared__ float red[];  // [rpi][C][K]
-  if (rl < rpi) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[((int64_t)rl * C + (cl + q * lanes_c) * 4 + e) * K + k] = s[q][k][e];
-  }
-  __syncthreads();
-  float* dst = srows + (int64_t)blockIdx.x * C * K;
-  for (int idx = threadIdx.x; idx < C * K; idx += 256) {
-    float tt = 0.f;
-    for (int q = 0; q < rpi; ++q) tt += red[(int64_t)q * C * K + idx];
-    dst[idx] = tt;
-  }
+  block_rows_out<K, 4>(s, ln, red, srows, C, lanes_c, rpi);
 }
 
+// >= 16 rows per thread, at most 1024 blocks; above 256 groups a block is one row lane
 int bn_bwd_reduce32_blocks(int64_t rows, int C) {
-  const int vpr = C / 4;
-  const int rpi = vpr >= 256 ? 1 : 256 / vpr;
-  int64_t b = (rows + rpi * 16 - 1) / (rpi * 16);
-  if (b > 1024) b = 1024;
-  return (int)(b < 1 ? 1 : b);
+  return col_plan(rows, C, 4, 2, 16, 1024, C / 4 > 256 ? 256 : 0).blocks;
 }
 
 void bn_bwd_reduce32_launch(const float* g, const float* mref, const float* y1, const float* coef1, const float* y2,
                             const float* coef2, double* slots, int blocks, int64_t rows, int C, hipStream_t s) {
   const int vpr = C / 4;
-  const int nv = vpr > 256 ? vpr / 256 : 1;
+  const int nv = vpr > 256 ? vpr / 256 : 1;  // float4 groups per thread
   if (nv > 2 || (vpr > 256 && vpr % 256 != 0))
     pdt_hip_fail("bn_bwd_reduce32: C must be <= 2048 (and a multiple of 1024 above 1024)", hipErrorInvalidValue,
                  __FILE__, __LINE__);
-  const int rpi = 256 / (vpr / nv);
   const int nbr = y2 ? 2 : 1;
-  Scratch part((size_t)blocks * C * nbr * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
-  const size_t smem = (size_t)rpi * C * nbr * 2 * sizeof(float);
+  const ColPlan p = col_plan(rows, C, 4 * nv, nbr * 2, 16, 1024);  // a thread's nv groups planned as one
   const bool mask = mref != nullptr;
-#define PDT_R32(M_, NB_, NV_)                                                                                \
-  if (mask == M_ && nbr == NB_ && nv == NV_) {                                                               \
-    hipLaunchKernelGGL((bn_bwd_reduce32_kernel<M_, NB_, NV_>), dim3(blocks), dim3(256), smem, s, g, mref, y1, \
-                       coef1, y2, coef2, srows, rows, C);                                                     \
-    stat_rows_reduce_launch(srows, blocks, C * nbr * 2, slots, s);                                           \
-    return;                                                                                                  \
+  col_reduce_run(blocks, C, nbr * 2, slots, s, [&](float* srows) {
+#define PDT_R32(M_, NB_, NV_)                                                                                 \
+  if (mask == M_ && nbr == NB_ && nv == NV_) {                                                                \
+    hipLaunchKernelGGL((bn_bwd_reduce32_kernel<M_, NB_, NV_>), dim3(blocks), dim3(256), p.lds, s, g, mref, y1, \
+                       coef1, y2, coef2, srows, rows, C, p.cvb, p.rpi);                                       \
+    return;                                                                                                   \
   }
-  PDT_R32(true, 1, 1) PDT_R32(true, 2, 1) PDT_R32(false, 1, 1) PDT_R32(false, 2, 1)
-  PDT_R32(true, 1, 2) PDT_R32(true, 2, 2) PDT_R32(false, 1, 2) PDT_R32(false, 2, 2)
+    PDT_R32(true, 1, 1) PDT_R32(true, 2, 1) PDT_R32(false, 1, 1) PDT_R32(false, 2, 1)
+    PDT_R32(true, 1, 2) PDT_R32(true, 2, 2) PDT_R32(false, 1, 2) PDT_R32(false, 2, 2)
 #undef PDT_R32
-  pdt_hip_fail("bn_bwd_reduce32: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
+    pdt_hip_fail("bn_bwd_reduce32: unsupported variant", hipErrorInvalidValue, __FILE__, __LINE__);
+  });
 }
 
 // dy_b = A_b*dz + B_b*y_b + C_b, dz = g * (mref > 0); optionally writes dz (identity-branch gradient)
@@ -1233,7 +1208,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply32_kernel(const float* __rest
 void bn_bwd_apply32_launch(const float* g, const float* mref, const float* y1, const float* b1, float* dy1,
                            const float* y2, const float* b2, float* dy2, float* dz, int64_t n, int C, hipStream_t s) {
   const int64_t n4 = n / 4;
-  dim3 gr(ew_blocks(n4)), bl(256);
+  dim3 gr(ew_blocks(n4, kEwCap)), bl(256);
   const bool mask = mref != nullptr, wdz = dz != nullptr;
   const int nbr = y2 ? 2 : 1;
 #define PDT_B32(M_, NB_, WZ_)                                                                                     \
@@ -1286,61 +1261,12 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool32_kernel(const float* __r
 void bn_relu_maxpool32_launch(const float* y, const float* coef, float* out, uint8_t* idx, int N, int H, int W, int C,
                               hipStream_t s) {
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(bn_relu_maxpool32_kernel, dim3(ew_blocks((int64_t)N * OH * OW * (C / 4))), dim3(256), 0, s, y,
+  hipLaunchKernelGGL(bn_relu_maxpool32_kernel, dim3(ew_blocks((int64_t)N * OH * OW * (C / 4), kEwCap)), dim3(256), 0, s, y,
                      coef, out, idx, N, H, W, C, OH, OW);
 }
 
-// gather-form max-pool backward fused with the ReLU mask recomputed from the BN input y
-__global__ __launch_bounds__(256) void maxpool_bwd_relu32_kernel(const float* __restrict__ dp, const uint8_t* __restrict__ idx,
-                                                                 const float* __restrict__ y, const float* __restrict__ coef,
-                                                                 float* __restrict__ dz, int N, int H, int W, int C, int OH,
-                                                                 int OW) {
-  const int cv = C / 4;
-  const int64_t total = (int64_t)N * H * W * cv;
-  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (int64_t)gridDim.x * 256) {
-    const int c0 = (int)(v % cv) * 4;
-    int64_t pix = v / cv;
-    const int w = (int)(pix % W);
-    pix /= W;
-    const int h = (int)(pix % H), n = (int)(pix / H);
-    f32x4v acc = {0.f, 0.f, 0.f, 0.f};
-    for (int oh = h / 2; oh <= (h + 1) / 2; ++oh) {
-      const int kh = h - (oh * 2 - 1);
-      if (oh >= OH || kh < 0 || kh > 2) continue;
-      for (int ow = w / 2; ow <= (w + 1) / 2; ++ow) {
-        const int kw = w - (ow * 2 - 1);
-        if (ow >= OW || kw < 0 || kw > 2) continue;
-        const uint8_t pos = (uint8_t)(kh * 3 + kw);
-        const int64_t o = (((int64_t)n * OH + oh) * OW + ow) * C + c0;
-        const uint32_t ib = *(const uint32_t*)(idx + o);
-        const f32x4v gv = *(const f32x4v*)(dp + o);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if ((uint8_t)(ib >> (8 * e)) == pos) acc[e] += gv[e];
-      }
-    }
-    const int64_t i = (((int64_t)n * H + h) * W + w) * C + c0;
-    const f32x4v yy = *(const f32x4v*)(y + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (!(yy[e] * coef[c0 + e] + coef[C + c0 + e] > 0.f)) acc[e] = 0.f;
-    *(f32x4v*)(dz + i) = acc;
-  }
-}
-
-void maxpool_bwd_relu32_launch(const float* dp, const uint8_t* idx, const float* y, const float* coef, float* dz, int N,
-                               int H, int W, int C, hipStream_t s) {
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(maxpool_bwd_relu32_kernel, dim3(ew_blocks((int64_t)N * H * W * (C / 4))), dim3(256), 0, s, dp, idx,
-                     y, coef, dz, N, H, W, C, OH, OW);
-}
-
-// The stem's backward tail without the dz tensor (N x H x W x C fp32, 3.85 GB at ResNet-18 bs1200): dz = max-pool
-// backward (gather over the <= 4 pooling windows covering a pixel, argmax routing) x ReLU mask (BN output > 0) is
-// recomputed from the pooled gradient, the argmax bytes and y0 by both the BN-backward reduce and the apply, instead
-// of maxpool_bwd_relu32 writing it and bn_bwd_reduce32 / bn_bwd_apply32 reading it back: ~28 -> ~14 GB of traffic.
-// The gather and the float operations are maxpool_bwd_relu32's, and the reduce's thread / row / block structure is
-// bn_bwd_reduce32's (NV = 1): the results equal the three separate passes' up to the compiler's fma contraction.
+// dz of 4 channels of the conv-output pixel (n, h, w): gather-form max-pool backward (the <= 4 pooling windows covering
+// the pixel, argmax routing) x the ReLU mask recomputed from the BN input yy
 PDT_DEVICE f32x4v stem_pool_dz32(const float* __restrict__ dp, const uint8_t* __restrict__ idx, const f32x4v yy,
                                  const float* __restrict__ coef, int n, int h, int w, int c0, int C, int OH, int OW) {
   f32x4v acc = {0.f, 0.f, 0.f, 0.f};
@@ -1365,20 +1291,53 @@ PDT_DEVICE f32x4v stem_pool_dz32(const float* __restrict__ dp, const uint8_t* __
   return acc;
 }
 
+// that dz written out (the unfused stem backward)
+__global__ __launch_bounds__(256) void maxpool_bwd_relu32_kernel(const float* __restrict__ dp, const uint8_t* __restrict__ idx,
+                                                                 const float* __restrict__ y, const float* __restrict__ coef,
+                                                                 float* __restrict__ dz, int N, int H, int W, int C, int OH,
+                                                                 int OW) {
+  const int cv = C / 4;
+  const int64_t total = (int64_t)N * H * W * cv;
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (int64_t)gridDim.x * 256) {
+    const int c0 = (int)(v % cv) * 4;
+    int64_t pix = v / cv;
+    const int w = (int)(pix % W);
+    pix /= W;
+    const int h = (int)(pix % H), n = (int)(pix / H);
+    const int64_t i = (((int64_t)n * H + h) * W + w) * C + c0;
+    *(f32x4v*)(dz + i) = stem_pool_dz32(dp, idx, *(const f32x4v*)(y + i), coef, n, h, w, c0, C, OH, OW);
+  }
+}
+
+void maxpool_bwd_relu32_launch(const float* dp, const uint8_t* idx, const float* y, const float* coef, float* dz, int N,
+                               int H, int W, int C, hipStream_t s) {
+  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
+  hipLaunchKernelGGL(maxpool_bwd_relu32_kernel, dim3(ew_blocks((int64_t)N * H * W * (C / 4), kEwCap)), dim3(256), 0, s, dp, idx,
+                     y, coef, dz, N, H, W, C, OH, OW);
+}
+
+// The stem's backward tail without the dz tensor (N x H x W x C fp32, 3.85 GB at ResNet-18 bs1200): dz = max-pool
+// backward (gather over the <= 4 pooling windows covering a pixel, argmax routing) x ReLU mask (BN output > 0) is
+// recomputed from the pooled gradient, the argmax bytes and y0 by both the BN-backward reduce and the apply, instead
+// of maxpool_bwd_relu32 writing it and bn_bwd_reduce32 / bn_bwd_apply32 reading it back: ~28 -> ~14 GB of traffic.
+// The gather and the float operations are maxpool_bwd_relu32's (stem_pool_dz32), and the reduce's thread / row / block
+// structure is bn_bwd_reduce32's (NV = 1): the results equal the three separate passes' up to the compiler's fma
+// contraction.
 __global__ __launch_bounds__(256) void stem_pool_bwd_reduce32_kernel(const float* __restrict__ dp,
                                                                      const uint8_t* __restrict__ idx,
                                                                      const float* __restrict__ y,
                                                                      const float* __restrict__ coef,
                                                                      float* __restrict__ srows, int N, int H, int W,
-                                                                     int C, int OH, int OW, FastDiv fw, FastDiv fh) {
-  const int lanes_c = C / 4, rpi = 256 / lanes_c;
-  const int cl = threadIdx.x % lanes_c, rl = threadIdx.x / lanes_c;
+                                                                     int C, int OH, int OW, FastDiv fw, FastDiv fh,
+                                                                     int cvb, int rpi) {
+  extern __shared__ float red[];  // [rpi][C][2]
+  const ColLane ln = col_lanes<4>(C, cvb, rpi);
   const int64_t rows = (int64_t)N * H * W;
-  const int c0 = cl * 4;
-  float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
-  if (rl < rpi) {
+  const int c0 = ln.c0;
+  float s[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  if (ln.active) {
     const f32x4v mean = *(const f32x4v*)(coef + 2 * C + c0), istd = *(const f32x4v*)(coef + 3 * C + c0);
-    for (int64_t r = (int64_t)blockIdx.x * rpi + rl; r < rows; r += (int64_t)gridDim.x * rpi) {
+    for (int64_t r = (int64_t)blockIdx.x * rpi + ln.rl; r < rows; r += (int64_t)gridDim.x * rpi) {
       const int pix = (int)r;
       const int nh = (int)fdiv((uint32_t)pix, fw), w = pix - nh * W;
       const int n = (int)fdiv((uint32_t)nh, fh), h = nh - n * H;
@@ -1387,40 +1346,25 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_reduce32_kernel(const float
       const f32x4v x1 = (yy - mean) * istd;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        s0[e] += dz[e];
-        s1[e] += dz[e] * x1[e];
+        s[0][e] += dz[e];
+        s[1][e] += dz[e] * x1[e];
       }
     }
   }
-  extern __shared__ float red[];  // [rpi][C][2]
-  if (rl < rpi) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[((int64_t)rl * C + c0 + e) * 2 + 0] = s0[e];
-      red[((int64_t)rl * C + c0 + e) * 2 + 1] = s1[e];
-    }
-  }
-  __syncthreads();
-  float* dst = srows + (int64_t)blockIdx.x * C * 2;
-  for (int i = threadIdx.x; i < C * 2; i += 256) {
-    float tt = 0.f;
-    for (int q = 0; q < rpi; ++q) tt += red[(int64_t)q * C * 2 + i];
-    dst[i] = tt;
-  }
+  block_rows_out<2>(s, ln, red, srows, C, cvb, rpi);
 }
 
+// the two stem reduces run `blocks` row blocks of the caller's choice (its numbers are part of the result bits), so the
+// plan only lays out the lanes; the widths they take (C / 4 divides 256) are the binding's check
 void stem_pool_bwd_reduce32_launch(const float* dp, const uint8_t* idx, const float* y, const float* coef, double* slots,
                                    int blocks, int N, int H, int W, int C, hipStream_t s) {
-  if (C % 4 != 0 || C / 4 > 256 || 256 % (C / 4) != 0)
-    pdt_hip_fail("stem_pool_bwd_reduce32: C / 4 must divide 256", hipErrorInvalidValue, __FILE__, __LINE__);
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   PDT_COUNT("stem_pool_bwd_fused32");
-  const int rpi = 256 / (C / 4);
-  Scratch part((size_t)blocks * C * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
-  hipLaunchKernelGGL(stem_pool_bwd_reduce32_kernel, dim3(blocks), dim3(256), (size_t)rpi * C * 2 * sizeof(float), s, dp,
-                     idx, y, coef, srows, N, H, W, C, OH, OW, make_fastdiv((uint32_t)W), make_fastdiv((uint32_t)H));
-  stat_rows_reduce_launch(srows, blocks, C * 2, slots, s);
+  const ColPlan p = col_plan((int64_t)N * H * W, C, 4, 2, 1, blocks);
+  col_reduce_run(blocks, C, 2, slots, s, [&](float* srows) {
+    hipLaunchKernelGGL(stem_pool_bwd_reduce32_kernel, dim3(blocks), dim3(256), p.lds, s, dp, idx, y, coef, srows, N, H, W,
+                       C, OH, OW, make_fastdiv((uint32_t)W), make_fastdiv((uint32_t)H), p.cvb, p.rpi);
+  });
 }
 
 // The stem's BN-backward sums without touching the 112x112 tensors: the pooled output IS relu(scale*y + shift) at the
@@ -1432,12 +1376,13 @@ void stem_pool_bwd_reduce32_launch(const float* dp, const uint8_t* idx, const fl
 __global__ __launch_bounds__(256) void stem_pool_bwd_reduce_out32_kernel(const float* __restrict__ dp,
                                                                          const float* __restrict__ out,
                                                                          const float* __restrict__ coef,
-                                                                         float* __restrict__ srows, int64_t rows, int C) {
-  const int lanes_c = C / 4, rpi = 256 / lanes_c;
-  const int cl = threadIdx.x % lanes_c, rl = threadIdx.x / lanes_c;
-  const int c0 = cl * 4;
-  float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
-  if (rl < rpi) {
+                                                                         float* __restrict__ srows, int64_t rows, int C,
+                                                                         int cvb, int rpi) {
+  extern __shared__ float red[];  // [rpi][C][2]
+  const ColLane ln = col_lanes<4>(C, cvb, rpi);
+  const int c0 = ln.c0;
+  float s[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  if (ln.active) {
     float rsc[4], sh[4], mu[4], is[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -1447,46 +1392,29 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_reduce_out32_kernel(const f
       mu[e] = coef[2 * C + c0 + e];
       is[e] = coef[3 * C + c0 + e];
     }
-    for (int64_t r = (int64_t)blockIdx.x * rpi + rl; r < rows; r += (int64_t)gridDim.x * rpi) {
+    for (int64_t r = (int64_t)blockIdx.x * rpi + ln.rl; r < rows; r += (int64_t)gridDim.x * rpi) {
       const f32x4v g = *(const f32x4v*)(dp + r * C + c0);
       const f32x4v ov = *(const f32x4v*)(out + r * C + c0);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float dz = ov[e] > 0.f ? g[e] : 0.f;
         const float xhat = rsc[e] != 0.f ? ((ov[e] - sh[e]) * rsc[e] - mu[e]) * is[e] : 0.f;
-        s0[e] += dz;
-        s1[e] += dz * xhat;
+        s[0][e] += dz;
+        s[1][e] += dz * xhat;
       }
     }
   }
-  extern __shared__ float red[];  // [rpi][C][2]
-  if (rl < rpi) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[((int64_t)rl * C + c0 + e) * 2 + 0] = s0[e];
-      red[((int64_t)rl * C + c0 + e) * 2 + 1] = s1[e];
-    }
-  }
-  __syncthreads();
-  float* dst = srows + (int64_t)blockIdx.x * C * 2;  // this block's own partial row (conv_fwd.h)
-  for (int i = threadIdx.x; i < C * 2; i += 256) {
-    float t = 0.f;
-    for (int q = 0; q < rpi; ++q) t += red[(int64_t)q * C * 2 + i];
-    dst[i] = t;
-  }
+  block_rows_out<2>(s, ln, red, srows, C, cvb, rpi);
 }
 
 void stem_pool_bwd_reduce_out32_launch(const float* dp, const float* out, const float* coef, double* slots, int blocks,
                                        int64_t rows, int C, hipStream_t s) {
-  if (C % 4 != 0 || C / 4 > 256 || 256 % (C / 4) != 0)
-    pdt_hip_fail("stem_pool_bwd_reduce_out32: C / 4 must divide 256", hipErrorInvalidValue, __FILE__, __LINE__);
   PDT_COUNT("stem_pool_bwd_reduce_out32");
-  const int rpi = 256 / (C / 4);
-  Scratch part((size_t)blocks * C * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
-  hipLaunchKernelGGL(stem_pool_bwd_reduce_out32_kernel, dim3(blocks), dim3(256), (size_t)rpi * C * 2 * sizeof(float), s,
-                     dp, out, coef, srows, rows, C);
-  stat_rows_reduce_launch(srows, blocks, C * 2, slots, s);
+  const ColPlan p = col_plan(rows, C, 4, 2, 1, blocks);
+  col_reduce_run(blocks, C, 2, slots, s, [&](float* srows) {
+    hipLaunchKernelGGL(stem_pool_bwd_reduce_out32_kernel, dim3(blocks), dim3(256), p.lds, s, dp, out, coef, srows, rows, C,
+                       p.cvb, p.rpi);
+  });
 }
 
 // dy = A*dz + B*y + C with dz recomputed (stem_pool_dz32): bn_bwd_apply32<false, 1, false> over maxpool_bwd_relu32's dz
@@ -1516,7 +1444,7 @@ void stem_pool_bwd_apply32_launch(const float* dp, const uint8_t* idx, const flo
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   if (C % 4 != 0 || ((C / 4) & (C / 4 - 1)) != 0)
     pdt_hip_fail("stem_pool_bwd_apply32: C / 4 must be a power of two", hipErrorInvalidValue, __FILE__, __LINE__);
-  hipLaunchKernelGGL(stem_pool_bwd_apply32_kernel, dim3(ew_blocks((int64_t)N * H * W * (C / 4))), dim3(256), 0, s, dp,
+  hipLaunchKernelGGL(stem_pool_bwd_apply32_kernel, dim3(ew_blocks((int64_t)N * H * W * (C / 4), kEwCap)), dim3(256), 0, s, dp,
                      idx, y, coef, b, dy, N, H, W, C, OH, OW, make_fastdiv((uint32_t)W), make_fastdiv((uint32_t)H));
 }
 
@@ -1545,11 +1473,11 @@ __global__ __launch_bounds__(256) void avgpool32_bwd_kernel(const float* __restr
 }
 
 void avgpool32_fwd_launch(const float* x, float* feat, int N, int HW, int C, int ldf, hipStream_t s) {
-  hipLaunchKernelGGL(avgpool32_fwd_kernel, dim3(ew_blocks((int64_t)N * C)), dim3(256), 0, s, x, feat, N, HW, C, ldf);
+  hipLaunchKernelGGL(avgpool32_fwd_kernel, dim3(ew_blocks((int64_t)N * C, kEwCap)), dim3(256), 0, s, x, feat, N, HW, C, ldf);
 }
 
 void avgpool32_bwd_launch(const float* dfeat, float* g, int N, int HW, int C, int ldf, hipStream_t s) {
-  hipLaunchKernelGGL(avgpool32_bwd_kernel, dim3(ew_blocks((int64_t)N * HW * C)), dim3(256), 0, s, dfeat, g, N, HW, C,
+  hipLaunchKernelGGL(avgpool32_bwd_kernel, dim3(ew_blocks((int64_t)N * HW * C, kEwCap)), dim3(256), 0, s, dfeat, g, N, HW, C,
                      ldf);
 }
 

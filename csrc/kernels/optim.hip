@@ -15,11 +15,7 @@
 
 namespace pdt {
 
-static int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  return (int)(b < 1 ? 1 : b);
-}
+constexpr int kEwCap = 8192;  // most blocks of a grid-stride elementwise kernel here
 
 __global__ __launch_bounds__(256) void nonfinite_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ found) {
   bool bad = false;
@@ -31,7 +27,7 @@ __global__ __launch_bounds__(256) void nonfinite_kernel(const float* __restrict_
 }
 
 void nonfinite_check_launch(const float* g, int64_t n, float* found, hipStream_t s) {
-  hipLaunchKernelGGL(nonfinite_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, g, n, found);
+  hipLaunchKernelGGL(nonfinite_kernel, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, g, n, found);
 }
 
 template <int DT>
@@ -64,10 +60,10 @@ void sgd_launch(int dtype, float* p, const float* g, float* buf, uint16_t* shado
                 float lr, float momentum, float wd, float gscale, const float* loss_scale, const float* found_inf,
                 bool first, hipStream_t s) {
   if (dtype == kBF16)
-    hipLaunchKernelGGL(sgd_kernel<kBF16>, dim3(ew_blocks(n)), dim3(256), 0, s, p, g, buf, shadow, wd_mask, n, lr, momentum,
+    hipLaunchKernelGGL(sgd_kernel<kBF16>, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, p, g, buf, shadow, wd_mask, n, lr, momentum,
                        wd, gscale, loss_scale, found_inf, (int)first);
   else
-    hipLaunchKernelGGL(sgd_kernel<kF16>, dim3(ew_blocks(n)), dim3(256), 0, s, p, g, buf, shadow, wd_mask, n, lr, momentum,
+    hipLaunchKernelGGL(sgd_kernel<kF16>, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, p, g, buf, shadow, wd_mask, n, lr, momentum,
                        wd, gscale, loss_scale, found_inf, (int)first);
 }
 
@@ -79,9 +75,9 @@ __global__ __launch_bounds__(256) void cast16_kernel(const float* __restrict__ p
 
 void cast16_launch(int dtype, const float* p, uint16_t* out, int64_t n, hipStream_t s) {
   if (dtype == kBF16)
-    hipLaunchKernelGGL(cast16_kernel<kBF16>, dim3(ew_blocks(n)), dim3(256), 0, s, p, out, n);
+    hipLaunchKernelGGL(cast16_kernel<kBF16>, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, p, out, n);
   else
-    hipLaunchKernelGGL(cast16_kernel<kF16>, dim3(ew_blocks(n)), dim3(256), 0, s, p, out, n);
+    hipLaunchKernelGGL(cast16_kernel<kF16>, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, p, out, n);
 }
 
 // 16-bit -> fp32 widening (gradient-compression epilogue of the native bucketer: bf16 all-reduce, fp32 grads)
@@ -93,9 +89,9 @@ __global__ __launch_bounds__(256) void widen16_kernel(const uint16_t* __restrict
 
 void widen16_launch(int dtype, const uint16_t* in, float* out, int64_t n, hipStream_t s) {
   if (dtype == kBF16)
-    hipLaunchKernelGGL(widen16_kernel<kBF16>, dim3(ew_blocks(n)), dim3(256), 0, s, in, out, n);
+    hipLaunchKernelGGL(widen16_kernel<kBF16>, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, in, out, n);
   else
-    hipLaunchKernelGGL(widen16_kernel<kF16>, dim3(ew_blocks(n)), dim3(256), 0, s, in, out, n);
+    hipLaunchKernelGGL(widen16_kernel<kF16>, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, in, out, n);
 }
 
 // GradScaler._amp_update_scale_: scale *= backoff on inf (tracker = 0), else tracker += 1 and
@@ -133,7 +129,7 @@ __global__ __launch_bounds__(256) void gather16_kernel(const uint16_t* __restric
 }
 
 void gather16_launch(const uint16_t* src, const int* idx, uint16_t* dst, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(gather16_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, src, idx, dst, n);
+  hipLaunchKernelGGL(gather16_kernel, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, src, idx, dst, n);
 }
 
 // Stem input: fp32 NCHW image batch -> 16-bit im2col rows [N*OH*OW][ldk], column k = (r*S + s)*C + c
@@ -181,10 +177,10 @@ void im2col_launch(int dtype, const float* x, uint16_t* out, int N, int C, int H
   const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
   const int64_t total = (int64_t)N * OH * OW * (ldk / 8);
   if (dtype == kBF16)
-    hipLaunchKernelGGL(im2col_kernel<kBF16>, dim3(ew_blocks(total)), dim3(256), 0, s, x, out, N, C, H, W, R, S, stride, pad,
+    hipLaunchKernelGGL(im2col_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, out, N, C, H, W, R, S, stride, pad,
                        OH, OW, ldk);
   else
-    hipLaunchKernelGGL(im2col_kernel<kF16>, dim3(ew_blocks(total)), dim3(256), 0, s, x, out, N, C, H, W, R, S, stride, pad,
+    hipLaunchKernelGGL(im2col_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, out, N, C, H, W, R, S, stride, pad,
                        OH, OW, ldk);
 }
 
@@ -281,10 +277,10 @@ void stem_pack_launch(int dtype, const float* x, uint16_t* out, int N, int C, in
   }
   const int64_t total = (int64_t)N * Hp * Wp;
   if (dtype == kBF16)
-    hipLaunchKernelGGL((stem_pack_kernel<kBF16, float>), dim3(ew_blocks(total)), dim3(256), 0, s, x, out, N, C, H, W,
+    hipLaunchKernelGGL((stem_pack_kernel<kBF16, float>), dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, out, N, C, H, W,
                        pad, Hp, Wp, nullptr, nullptr, make_fastdiv((uint32_t)Wp), make_fastdiv((uint32_t)Hp));
   else
-    hipLaunchKernelGGL((stem_pack_kernel<kF16, float>), dim3(ew_blocks(total)), dim3(256), 0, s, x, out, N, C, H, W,
+    hipLaunchKernelGGL((stem_pack_kernel<kF16, float>), dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, out, N, C, H, W,
                        pad, Hp, Wp, nullptr, nullptr, make_fastdiv((uint32_t)Wp), make_fastdiv((uint32_t)Hp));
 }
 
@@ -292,10 +288,10 @@ void stem_pack_u8_launch(int dtype, const uint8_t* x, uint16_t* out, int N, int 
                          int Wp, const float* scale, const float* shift, hipStream_t s) {
   const int64_t total = (int64_t)N * Hp * Wp;
   if (dtype == kBF16)
-    hipLaunchKernelGGL((stem_pack_kernel<kBF16, uint8_t>), dim3(ew_blocks(total)), dim3(256), 0, s, x, out, N, C, H,
+    hipLaunchKernelGGL((stem_pack_kernel<kBF16, uint8_t>), dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, out, N, C, H,
                        W, pad, Hp, Wp, scale, shift, make_fastdiv((uint32_t)Wp), make_fastdiv((uint32_t)Hp));
   else
-    hipLaunchKernelGGL((stem_pack_kernel<kF16, uint8_t>), dim3(ew_blocks(total)), dim3(256), 0, s, x, out, N, C, H,
+    hipLaunchKernelGGL((stem_pack_kernel<kF16, uint8_t>), dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, out, N, C, H,
                        W, pad, Hp, Wp, scale, shift, make_fastdiv((uint32_t)Wp), make_fastdiv((uint32_t)Hp));
 }
 
@@ -308,7 +304,7 @@ __global__ __launch_bounds__(256) void gather32_kernel(const float* __restrict__
 }
 
 void gather32_launch(const float* src, const int* idx, float* dst, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(gather32_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, src, idx, dst, n);
+  hipLaunchKernelGGL(gather32_kernel, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, src, idx, dst, n);
 }
 
 // dst[idx[i]] = src[i]: the inverse of gather32 over distinct indices (DataParallel replicas receive the fp32
@@ -320,7 +316,7 @@ __global__ __launch_bounds__(256) void scatter32_kernel(const float* __restrict_
 
 void scatter32_launch(const float* src, const int* idx, float* dst, int64_t n, hipStream_t s) {
   if (n == 0) return;
-  hipLaunchKernelGGL(scatter32_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, src, idx, dst, n);
+  hipLaunchKernelGGL(scatter32_kernel, dim3(ew_blocks(n, kEwCap)), dim3(256), 0, s, src, idx, dst, n);
 }
 
 }  // namespace pdt

@@ -10,16 +10,12 @@
 //     each input pixel and writes dy = A*dz + B*y + C directly (SURVEY K9 + K7/K8 fused).
 //   * avgpool (global, HxW -> 1) forward and backward.
 #include "../common.h"
-#include "conv_fwd.h"
+#include "col_reduce.h"
 #include "pool.h"
 
 namespace pdt {
 
-static int ew_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 16384) b = 16384;
-  return (int)(b < 1 ? 1 : b);
-}
+constexpr int kEwCap = 16384;  // most blocks of a grid-stride elementwise kernel here
 
 template <int DT>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const uint16_t* __restrict__ y, const float* __restrict__ coef,
@@ -96,10 +92,10 @@ void bn_relu_maxpool_launch(int dtype, const uint16_t* y, const float* coef, uin
   const int OH = (H + 2 * pad - 3) / 2 + 1, OW = (W + 2 * pad - 3) / 2 + 1;
   const int64_t total = (int64_t)N * OH * OW * (C / 8);
   if (dtype == kBF16)
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<kBF16>, dim3(ew_blocks(total)), dim3(256), 0, s, y, coef, out, idx, N, H, W,
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, y, coef, out, idx, N, H, W,
                        C, OH, OW, pad);
   else
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<kF16>, dim3(ew_blocks(total)), dim3(256), 0, s, y, coef, out, idx, N, H, W,
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, y, coef, out, idx, N, H, W,
                        C, OH, OW, pad);
 }
 
@@ -165,10 +161,10 @@ void maxpool_bwd_relu_launch(int dtype, const uint16_t* dp, const uint8_t* idx, 
   const int OH = (H + 2 * pad - 3) / 2 + 1, OW = (W + 2 * pad - 3) / 2 + 1;
   const int64_t total = (int64_t)N * H * W * (C / 8);
   if (dtype == kBF16)
-    hipLaunchKernelGGL(maxpool_bwd_relu_kernel<kBF16>, dim3(ew_blocks(total)), dim3(256), 0, s, dp, idx, y, coef, dz, N, H,
+    hipLaunchKernelGGL(maxpool_bwd_relu_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dp, idx, y, coef, dz, N, H,
                        W, C, OH, OW, pad);
   else
-    hipLaunchKernelGGL(maxpool_bwd_relu_kernel<kF16>, dim3(ew_blocks(total)), dim3(256), 0, s, dp, idx, y, coef, dz, N, H,
+    hipLaunchKernelGGL(maxpool_bwd_relu_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dp, idx, y, coef, dz, N, H,
                        W, C, OH, OW, pad);
 }
 
@@ -182,33 +178,32 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_reduce_kernel(const uint16_
                                                                    const uint16_t* __restrict__ y,
                                                                    const float* __restrict__ coef,
                                                                    float* __restrict__ srows, int N, int H, int W,
-                                                                   int C, int OH, int OW) {
+                                                                   int C, int OH, int OW, int cvb, int rpi) {
   using E = E16<DT>;
-  const int vpr = C / 8;
-  const int rpi = 256 / vpr;
-  const int cv = threadIdx.x % vpr, rl = threadIdx.x / vpr;
-  const int c0 = cv * 8;
-  float sc[8], sh[8], mu[8], is[8], s0[8], s1[8];
+  extern __shared__ float red[];  // [rpi][C][2]
+  const ColLane ln = col_lanes<8>(C, cvb, rpi);
+  const int c0 = ln.c0;
+  float sc[8], sh[8], mu[8], is[8], s[2][8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     sc[e] = coef[c0 + e];
     sh[e] = coef[C + c0 + e];
     mu[e] = coef[2 * C + c0 + e];
     is[e] = coef[3 * C + c0 + e];
-    s0[e] = 0.f;
-    s1[e] = 0.f;
+    s[0][e] = 0.f;
+    s[1][e] = 0.f;
   }
   const int64_t rows = (int64_t)N * OH * OW;
-  if (rl < rpi) {
-    for (int64_t r = (int64_t)blockIdx.x * rpi + rl; r < rows; r += (int64_t)gridDim.x * rpi) {
+  if (ln.active) {
+    for (int64_t r = (int64_t)blockIdx.x * rpi + ln.rl; r < rows; r += (int64_t)gridDim.x * rpi) {
       const int ow = (int)(r % OW);
       const int64_t t = r / OW;
       const int oh = (int)(t % OH);
       const int n = (int)(t / OH);
       const int64_t o = r * C + c0;
       const uint2 ib = *(const uint2*)(idx + o);
-      const uint4 g = *(const uint4*)(dp + o);
-      const uint32_t gw[4] = {g.x, g.y, g.z, g.w};
+      uint16_t gh[8];
+      unpack8(*(const uint4*)(dp + o), gh);
       const uint16_t* ybase = y + ((int64_t)n * H * W) * C + c0;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -219,46 +214,27 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_reduce_kernel(const uint16_
         const int kh = pos / 3, kw = pos - 3 * (pos / 3);
         const int h = oh * 2 - 1 + kh, w = ow * 2 - 1 + kw;  // always inside (argmax is a valid tap)
         const float yv = E::to_f(ybase[((int64_t)h * W + w) * C + e]);
-        const float dz =
-            (live && yv * sc[e] + sh[e] > 0.f) ? E::to_f((uint16_t)(gw[e >> 1] >> (16 * (e & 1)))) : 0.f;
-        s0[e] += dz;
-        s1[e] += dz * (yv - mu[e]) * is[e];
+        const float dz = (live && yv * sc[e] + sh[e] > 0.f) ? E::to_f(gh[e]) : 0.f;
+        s[0][e] += dz;
+        s[1][e] += dz * (yv - mu[e]) * is[e];
       }
     }
   }
-  extern __shared__ float red[];  // [rpi][C][2]
-  if (rl < rpi) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[((int64_t)rl * C + c0 + e) * 2 + 0] = s0[e];
-      red[((int64_t)rl * C + c0 + e) * 2 + 1] = s1[e];
-    }
-  }
-  __syncthreads();
-  float* dst = srows + (int64_t)blockIdx.x * C * 2;  // this block's own partial row (conv_fwd.h)
-  for (int i = threadIdx.x; i < C * 2; i += 256) {
-    float t = 0.f;
-    for (int q = 0; q < rpi; ++q) t += red[(int64_t)q * C * 2 + i];
-    dst[i] = t;
-  }
+  block_rows_out<2>(s, ln, red, srows, C, cvb, rpi);
 }
 
 void stem_pool_bwd_reduce_launch(int dtype, const uint16_t* dp, const uint8_t* idx, const uint16_t* y,
                                  const float* coef, double* slots, int N, int H, int W, int C, hipStream_t s) {
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  const int rpi = 256 / (C / 8);
-  int64_t blocks = ((int64_t)N * OH * OW + rpi * 8 - 1) / (rpi * 8);
-  if (blocks > 4096) blocks = 4096;
-  const size_t smem = (size_t)rpi * C * 2 * sizeof(float);
-  Scratch part((size_t)blocks * C * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
-  if (dtype == kBF16)
-    hipLaunchKernelGGL(stem_pool_bwd_reduce_kernel<kBF16>, dim3((int)blocks), dim3(256), smem, s, dp, idx, y, coef, srows,
-                       N, H, W, C, OH, OW);
-  else
-    hipLaunchKernelGGL(stem_pool_bwd_reduce_kernel<kF16>, dim3((int)blocks), dim3(256), smem, s, dp, idx, y, coef, srows,
-                       N, H, W, C, OH, OW);
-  stat_rows_reduce_launch(srows, (int)blocks, C * 2, slots, s);
+  const ColPlan p = col_plan((int64_t)N * OH * OW, C, 8, 2, 8, 4096);  // >= 8 rows per thread, at most 4096 blocks
+  col_reduce_run(p.blocks, C, 2, slots, s, [&](float* srows) {
+    if (dtype == kBF16)
+      hipLaunchKernelGGL(stem_pool_bwd_reduce_kernel<kBF16>, dim3(p.blocks), dim3(256), p.lds, s, dp, idx, y, coef, srows,
+                         N, H, W, C, OH, OW, p.cvb, p.rpi);
+    else
+      hipLaunchKernelGGL(stem_pool_bwd_reduce_kernel<kF16>, dim3(p.blocks), dim3(256), p.lds, s, dp, idx, y, coef, srows,
+                         N, H, W, C, OH, OW, p.cvb, p.rpi);
+  });
 }
 
 // Stem backward, pass 1 without touching the 112x112 tensor: the pooled output IS relu(scale*y + shift)
@@ -271,13 +247,12 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_reduce_out_kernel(const uin
                                                                        const uint16_t* __restrict__ out,
                                                                        const float* __restrict__ coef,
                                                                        float* __restrict__ srows, int64_t rows,
-                                                                       int C) {
+                                                                       int C, int cvb, int rpi) {
   using E = E16<DT>;
-  const int vpr = C / 8;
-  const int rpi = 256 / vpr;
-  const int cv = threadIdx.x % vpr, rl = threadIdx.x / vpr;
-  const int c0 = cv * 8;
-  float rsc[8], sh[8], mu[8], is[8], s0[8], s1[8];
+  extern __shared__ float red[];  // [rpi][C][2]
+  const ColLane ln = col_lanes<8>(C, cvb, rpi);
+  const int c0 = ln.c0;
+  float rsc[8], sh[8], mu[8], is[8], s[2][8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float sc = coef[c0 + e];
@@ -285,40 +260,27 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_reduce_out_kernel(const uin
     sh[e] = coef[C + c0 + e];
     mu[e] = coef[2 * C + c0 + e];
     is[e] = coef[3 * C + c0 + e];
-    s0[e] = 0.f;
-    s1[e] = 0.f;
+    s[0][e] = 0.f;
+    s[1][e] = 0.f;
   }
-  if (rl < rpi) {
-    for (int64_t r = (int64_t)blockIdx.x * rpi + rl; r < rows; r += (int64_t)gridDim.x * rpi) {
+  if (ln.active) {
+    for (int64_t r = (int64_t)blockIdx.x * rpi + ln.rl; r < rows; r += (int64_t)gridDim.x * rpi) {
       const int64_t o = r * C + c0;
       const uint4 g = *(const uint4*)(dp + o);
       const uint4 q = *(const uint4*)(out + o);
+      // decoded by hand, not by unpack8: with it the fp16 instantiation's load of `out` compiles to five narrower loads
       const uint32_t gw[4] = {g.x, g.y, g.z, g.w}, qw[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float ov = E::to_f((uint16_t)(qw[e >> 1] >> (16 * (e & 1))));
         const float dz = ov > 0.f ? E::to_f((uint16_t)(gw[e >> 1] >> (16 * (e & 1)))) : 0.f;
         const float xhat = rsc[e] != 0.f ? ((ov - sh[e]) * rsc[e] - mu[e]) * is[e] : 0.f;
-        s0[e] += dz;
-        s1[e] += dz * xhat;
+        s[0][e] += dz;
+        s[1][e] += dz * xhat;
       }
     }
   }
-  extern __shared__ float red[];  // [rpi][C][2]
-  if (rl < rpi) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[((int64_t)rl * C + c0 + e) * 2 + 0] = s0[e];
-      red[((int64_t)rl * C + c0 + e) * 2 + 1] = s1[e];
-    }
-  }
-  __syncthreads();
-  float* dst = srows + (int64_t)blockIdx.x * C * 2;  // this block's own partial row (conv_fwd.h)
-  for (int i = threadIdx.x; i < C * 2; i += 256) {
-    float t = 0.f;
-    for (int q = 0; q < rpi; ++q) t += red[(int64_t)q * C * 2 + i];
-    dst[i] = t;
-  }
+  block_rows_out<2>(s, ln, red, srows, C, cvb, rpi);
 }
 
 void stem_pool_bwd_reduce_out_launch(int dtype, const uint16_t* dp, const uint16_t* out, const float* coef,
@@ -331,19 +293,15 @@ void stem_pool_bwd_reduce_out_launch(int dtype, const uint16_t* dp, const uint16
 // gradient and the pooled output are read, ``rows`` pooled pixels
 void pooled_bwd_reduce_launch(int dtype, const uint16_t* dp, const uint16_t* out, const float* coef, double* slots,
                               int64_t rows, int C, hipStream_t s) {
-  const int rpi = 256 / (C / 8);
-  int64_t blocks = (rows + rpi * 8 - 1) / (rpi * 8);
-  if (blocks > 2048) blocks = 2048;
-  const size_t smem = (size_t)rpi * C * 2 * sizeof(float);
-  Scratch part((size_t)blocks * C * 2 * sizeof(float), s);
-  float* srows = part.as<float>();
-  if (dtype == kBF16)
-    hipLaunchKernelGGL(stem_pool_bwd_reduce_out_kernel<kBF16>, dim3((int)blocks), dim3(256), smem, s, dp, out, coef,
-                       srows, rows, C);
-  else
-    hipLaunchKernelGGL(stem_pool_bwd_reduce_out_kernel<kF16>, dim3((int)blocks), dim3(256), smem, s, dp, out, coef,
-                       srows, rows, C);
-  stat_rows_reduce_launch(srows, (int)blocks, C * 2, slots, s);
+  const ColPlan p = col_plan(rows, C, 8, 2, 8, 2048);  // >= 8 rows per thread, at most 2048 blocks
+  col_reduce_run(p.blocks, C, 2, slots, s, [&](float* srows) {
+    if (dtype == kBF16)
+      hipLaunchKernelGGL(stem_pool_bwd_reduce_out_kernel<kBF16>, dim3(p.blocks), dim3(256), p.lds, s, dp, out, coef,
+                         srows, rows, C, p.cvb, p.rpi);
+    else
+      hipLaunchKernelGGL(stem_pool_bwd_reduce_out_kernel<kF16>, dim3(p.blocks), dim3(256), p.lds, s, dp, out, coef,
+                         srows, rows, C, p.cvb, p.rpi);
+  });
 }
 
 // Stem backward, pass 2: dy = A*dz + B*y + Cc at every conv-output element, with dz gathered from the
@@ -437,10 +395,10 @@ void stem_pool_bwd_apply_launch(int dtype, const uint16_t* dp, const uint8_t* id
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)N * OH * OW * (C / 8);
   if (dtype == kBF16)
-    hipLaunchKernelGGL(stem_pool_bwd_apply_kernel<kBF16>, dim3(ew_blocks(total)), dim3(256), 0, s, dp, idx, y, coef,
+    hipLaunchKernelGGL(stem_pool_bwd_apply_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dp, idx, y, coef,
                        bcoef, dy, N, H, W, C, OH, OW);
   else
-    hipLaunchKernelGGL(stem_pool_bwd_apply_kernel<kF16>, dim3(ew_blocks(total)), dim3(256), 0, s, dp, idx, y, coef,
+    hipLaunchKernelGGL(stem_pool_bwd_apply_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dp, idx, y, coef,
                        bcoef, dy, N, H, W, C, OH, OW);
 }
 
@@ -496,17 +454,17 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const uint16_t* __rest
 void avgpool_fwd_launch(int dtype, const uint16_t* x, uint16_t* feat, int N, int HW, int C, int ldf, hipStream_t s) {
   const int64_t total = (int64_t)N * (C / 8);
   if (dtype == kBF16)
-    hipLaunchKernelGGL(avgpool_fwd_kernel<kBF16>, dim3(ew_blocks(total)), dim3(256), 0, s, x, feat, N, HW, C, ldf);
+    hipLaunchKernelGGL(avgpool_fwd_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, feat, N, HW, C, ldf);
   else
-    hipLaunchKernelGGL(avgpool_fwd_kernel<kF16>, dim3(ew_blocks(total)), dim3(256), 0, s, x, feat, N, HW, C, ldf);
+    hipLaunchKernelGGL(avgpool_fwd_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, x, feat, N, HW, C, ldf);
 }
 
 void avgpool_bwd_launch(int dtype, const uint16_t* dfeat, uint16_t* g, int N, int HW, int C, int ldf, hipStream_t s) {
   const int64_t total = (int64_t)N * HW * (C / 8);
   if (dtype == kBF16)
-    hipLaunchKernelGGL(avgpool_bwd_kernel<kBF16>, dim3(ew_blocks(total)), dim3(256), 0, s, dfeat, g, N, HW, C, ldf);
+    hipLaunchKernelGGL(avgpool_bwd_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dfeat, g, N, HW, C, ldf);
   else
-    hipLaunchKernelGGL(avgpool_bwd_kernel<kF16>, dim3(ew_blocks(total)), dim3(256), 0, s, dfeat, g, N, HW, C, ldf);
+    hipLaunchKernelGGL(avgpool_bwd_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dfeat, g, N, HW, C, ldf);
 }
 
 }  // namespace pdt

@@ -15,11 +15,7 @@
 
 namespace pdt {
 
-static int vgg_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 65536) b = 65536;
-  return (int)(b < 1 ? 1 : b);
-}
+constexpr int kEwCap = 65536;  // most blocks of a grid-stride elementwise kernel here
 
 template <int DT>
 __global__ __launch_bounds__(256) void bn_relu_maxpool2_kernel(const uint16_t* __restrict__ y,
@@ -75,10 +71,10 @@ void bn_relu_maxpool2_launch(int dtype, const uint16_t* y, const float* coef, ui
   const int64_t total = N * OH * OW * (C / 8);
   if (total == 0) return;
   if (dtype == kBF16)
-    hipLaunchKernelGGL(bn_relu_maxpool2_kernel<kBF16>, dim3(vgg_blocks(total)), dim3(256), 0, s, y, coef, out, idx,
+    hipLaunchKernelGGL(bn_relu_maxpool2_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, y, coef, out, idx,
                        total, W, C, OH, OW);
   else
-    hipLaunchKernelGGL(bn_relu_maxpool2_kernel<kF16>, dim3(vgg_blocks(total)), dim3(256), 0, s, y, coef, out, idx,
+    hipLaunchKernelGGL(bn_relu_maxpool2_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, y, coef, out, idx,
                        total, W, C, OH, OW);
 }
 
@@ -156,7 +152,7 @@ void maxpool2_bwd_launch(int dtype, const uint16_t* dp, const uint8_t* idx, cons
   const int OH = H / 2, OW = W / 2;
   const int64_t total = N * OH * OW * (C / 8);
   if (total == 0) return;
-  const dim3 g(vgg_blocks(total)), b(256);
+  const dim3 g(ew_blocks(total, kEwCap)), b(256);
   if (bcoef != nullptr) {
     if (dtype == kBF16)
       hipLaunchKernelGGL((maxpool2_bwd_kernel<kBF16, true>), g, b, 0, s, dp, idx, out, y, bcoef, dy, total, W, C, OH, OW);
@@ -221,10 +217,10 @@ void fc_act_fwd_launch(int dtype, const uint16_t* z, const float* bias, uint16_t
     scale = (float)(1.0 / (1.0 - p));
   }
   if (dtype == kBF16)
-    hipLaunchKernelGGL(fc_act_fwd_kernel<kBF16>, dim3(vgg_blocks(total)), dim3(256), 0, s, z, bias, out, total, F, thr,
+    hipLaunchKernelGGL(fc_act_fwd_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, z, bias, out, total, F, thr,
                        scale, seed);
   else
-    hipLaunchKernelGGL(fc_act_fwd_kernel<kF16>, dim3(vgg_blocks(total)), dim3(256), 0, s, z, bias, out, total, F, thr,
+    hipLaunchKernelGGL(fc_act_fwd_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, z, bias, out, total, F, thr,
                        scale, seed);
 }
 
@@ -258,9 +254,9 @@ void fc_act_bwd_launch(int dtype, const uint16_t* dh, const uint16_t* out, uint1
   if (total == 0) return;
   const float scale = p > 0.0 ? (float)(1.0 / (1.0 - p)) : 1.f;
   if (dtype == kBF16)
-    hipLaunchKernelGGL(fc_act_bwd_kernel<kBF16>, dim3(vgg_blocks(total)), dim3(256), 0, s, dh, out, dz, total, scale);
+    hipLaunchKernelGGL(fc_act_bwd_kernel<kBF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dh, out, dz, total, scale);
   else
-    hipLaunchKernelGGL(fc_act_bwd_kernel<kF16>, dim3(vgg_blocks(total)), dim3(256), 0, s, dh, out, dz, total, scale);
+    hipLaunchKernelGGL(fc_act_bwd_kernel<kF16>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, dh, out, dz, total, scale);
 }
 
 // NHWC [N][HW][C] <-> torchvision's flatten order [N][C][HW] (the classifier's input features)
@@ -285,9 +281,9 @@ void nhwc_nchw16_launch(const uint16_t* src, uint16_t* dst, int64_t N, int HW, i
   const int64_t total = N * HW * C;
   if (total == 0) return;
   if (to_nchw)
-    hipLaunchKernelGGL(nhwc_nchw16_kernel<true>, dim3(vgg_blocks(total)), dim3(256), 0, s, src, dst, total, HW, C);
+    hipLaunchKernelGGL(nhwc_nchw16_kernel<true>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, src, dst, total, HW, C);
   else
-    hipLaunchKernelGGL(nhwc_nchw16_kernel<false>, dim3(vgg_blocks(total)), dim3(256), 0, s, src, dst, total, HW, C);
+    hipLaunchKernelGGL(nhwc_nchw16_kernel<false>, dim3(ew_blocks(total, kEwCap)), dim3(256), 0, s, src, dst, total, HW, C);
 }
 
 // coef = [1 | bias | 0 | 1]: a conv bias + ReLU expressed as the BatchNorm coefficient block the fused kernels read
