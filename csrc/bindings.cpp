@@ -182,12 +182,14 @@ void set_dgrad_geom(const char* op, pdt::ConvGeom& a, int64_t N, int64_t P, int6
   a.M = maxM;
 }
 
+// max_wg (optional, last): cap on the persistent ping-pong kernel's workgroup count (ConvFwdArgs::max_wg; 0 = one per CU)
 void conv_fwd(const Tensor& x, const Tensor& w, Tensor& y, const OptT& res, const OptT& stats, int64_t N, int64_t H,
               int64_t W, int64_t C, int64_t Kout, int64_t T, int64_t U, int64_t Pm, int64_t Qm, int64_t ist_h,
               int64_t ist_w, int64_t ioff_h, int64_t ioff_w, int64_t tstep_h, int64_t tstep_w, int64_t OH, int64_t OW,
               int64_t ost_h, int64_t ost_w, int64_t ooff_h, int64_t ooff_w, int64_t bm, int64_t bn, int64_t bk,
-              int64_t cs) {
+              int64_t cs, int64_t max_wg) {
   const int dt = dt16(x, "x");
+  TORCH_CHECK(max_wg >= 0 && max_wg < (int64_t(1) << 30), "conv_fwd: bad max_wg");
   if (cs <= 0) cs = C;
   TORCH_CHECK(dt16(w, "w") == dt && dt16(y, "y") == dt, "conv_fwd: mixed dtypes");
   TORCH_CHECK(x.numel() == N * H * W * cs, "conv_fwd: x has ", x.numel(), " elements, geometry needs ", N * H * W * cs);
@@ -229,6 +231,7 @@ void conv_fwd(const Tensor& x, const Tensor& w, Tensor& y, const OptT& res, cons
   a.OH = OH; a.OW = OW; a.ost_h = ost_h; a.ost_w = ost_w; a.ooff_h = ooff_h; a.ooff_w = ooff_w;
   TORCH_CHECK(M < (int64_t(1) << 31), "conv_fwd: N*Pm*Qm must be < 2^31 (32-bit pixel indexing)");
   a.M = M;
+  a.max_wg = (int)max_wg;
   pdt::conv_fwd_launch(a, dt, (int)bm, (int)bn, (int)bk, cur_stream());
   launched("conv_fwd_launch");
 }
@@ -314,12 +317,14 @@ int64_t dgrad_persistent_kind(int64_t K, int64_t C, int64_t bnb, int64_t stride,
 
 // Backward-data of a (strided) conv in ONE launch: phases = [(ph, pw, T, U, ioff_h, ioff_w, woff), ...]
 // over dY [N,P,Q,K] -> dX [N,H,W,C] (+ residual), wt = concatenated per-phase [C][T][U][K] weights.
+// max_wg: as conv_fwd
 void conv_dgrad_impl(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT& res, int64_t N, int64_t P,
                      int64_t Q, int64_t K, int64_t C, int64_t H, int64_t W, int64_t stride,
                      const std::vector<std::vector<int64_t>>& phases, int64_t bm, int64_t bn, int64_t bk, int64_t bnb,
                      const OptT& bn_y1, const OptT& bn_coef1, const OptT& bn_y2, const OptT& bn_coef2,
-                     const OptT& bn_mask, const OptT& bn_slots, int64_t res_phase) {
+                     const OptT& bn_mask, const OptT& bn_slots, int64_t res_phase, int64_t max_wg) {
   const int dt = dt16(dy, "dy");
+  TORCH_CHECK(max_wg >= 0 && max_wg < (int64_t(1) << 30), "conv_dgrad: bad max_wg");
   TORCH_CHECK(dt16(wt, "wt") == dt && dt16(dx, "dx") == dt, "conv_dgrad: mixed dtypes");
   TORCH_CHECK(dy.numel() == N * P * Q * K && dx.numel() == N * H * W * C, "conv_dgrad: size mismatch");
   TORCH_CHECK(dy.numel() < (int64_t(1) << 30) && wt.numel() < (int64_t(1) << 30),
@@ -388,6 +393,7 @@ void conv_dgrad_impl(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT&
     launched("conv1x1x_bnb");
     return;
   }
+  a.max_wg = (int)max_wg;
   pdt::conv_fwd_launch(a, dt, (int)bm, (int)bn, (int)bk, cur_stream());
   launched("conv_fwd_launch");
 }
@@ -395,7 +401,7 @@ void conv_dgrad_impl(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT&
 void conv_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, const OptT& res, int64_t N, int64_t P, int64_t Q,
                 int64_t K, int64_t C, int64_t H, int64_t W, int64_t stride, const std::vector<std::vector<int64_t>>& phases,
                 int64_t bm, int64_t bn, int64_t bk) {
-  conv_dgrad_impl(dy, wt, dx, res, N, P, Q, K, C, H, W, stride, phases, bm, bn, bk, 0, {}, {}, {}, {}, {}, {}, -1);
+  conv_dgrad_impl(dy, wt, dx, res, N, P, Q, K, C, H, W, stride, phases, bm, bn, bk, 0, {}, {}, {}, {}, {}, {}, -1, 0);
 }
 
 // 1x1 / stride-1 conv, 64 -> 256 channels, as the persistent store-overlapped kernel (conv1x1.hip): y[M][256] from
@@ -1555,10 +1561,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     std::lock_guard<std::mutex> lk(r.mu);
     for (auto& e : r.entries) __atomic_store_n(e.second.get(), 0LL, __ATOMIC_RELAXED);
   });
-  m.def("conv_fwd", &conv_fwd);
+  m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("res"), py::arg("stats"), py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("C"), py::arg("Kout"), py::arg("T"), py::arg("U"), py::arg("Pm"), py::arg("Qm"),
+        py::arg("ist_h"), py::arg("ist_w"), py::arg("ioff_h"), py::arg("ioff_w"), py::arg("tstep_h"), py::arg("tstep_w"),
+        py::arg("OH"), py::arg("OW"), py::arg("ost_h"), py::arg("ost_w"), py::arg("ooff_h"), py::arg("ooff_w"),
+        py::arg("bm"), py::arg("bn"), py::arg("bk"), py::arg("cs"), py::arg("max_wg") = 0);
   m.def("conv_m_tiles", &conv_m_tiles);
   m.def("conv_dgrad", &conv_dgrad);
-  m.def("conv_dgrad_bn", &conv_dgrad_impl);
+  m.def("conv_dgrad_bn", &conv_dgrad_impl, py::arg("dy"), py::arg("wt"), py::arg("dx"), py::arg("res"), py::arg("N"),
+        py::arg("P"), py::arg("Q"), py::arg("K"), py::arg("C"), py::arg("H"), py::arg("W"), py::arg("stride"),
+        py::arg("phases"), py::arg("bm"), py::arg("bn"), py::arg("bk"), py::arg("bnb"), py::arg("bn_y1"),
+        py::arg("bn_coef1"), py::arg("bn_y2"), py::arg("bn_coef2"), py::arg("bn_mask"), py::arg("bn_slots"),
+        py::arg("res_phase"), py::arg("max_wg") = 0);
   m.def("conv_wgrad_plan", &conv_wgrad_plan);
   m.def("conv1x1_c64_supported", &conv1x1_c64_supported);
   m.def("conv1x1_c64", &conv1x1_c64, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stats"), py::arg("M"),

@@ -57,6 +57,9 @@ struct ConvFwdArgs : ConvGeom {
   int nslice = 0;
   int64_t slice_wstride = 0;
   int srows_coff = 0;  // kernel-local: this block's column offset (channels) in the statistics partial rows
+  // persistent ping-pong kernel (conv_pp_kernel): cap on the number of workgroups that walk the tiles; 0 = one per
+  // CU.  Results do not depend on it (a test varies it to move the tile boundaries between workgroups).
+  int max_wg = 0;
 };
 
 void conv_fwd_launch(const ConvFwdArgs& a, int dtype, int bm, int bn, int bk, hipStream_t s);

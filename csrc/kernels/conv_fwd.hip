@@ -43,7 +43,7 @@ PDT_DEVICE int swz(int row) { return (row >> 1) & (CHUNKS - 1); }
 // Shared epilogue of the implicit-GEMM conv kernels: the wave's accumulators acc[i][j] hold output
 // channels n = n0 + wn*WN + i*16 + 4*fq + r of pixel m = m0 + wm*WM + j*16 + fr.
 // RES: 0 no residual | 1 residual in the output's layout | 2 compact residual of sub-pixel phase a.res_phase
-// (ConvFwdArgs::res_phase), indexed by GEMM row; its loads stay unconditional (in range on every phase) and
+// (ConvFwdArgs::res_phase), indexed by GEMM row (``ph`` is the tile's own phase); its loads stay unconditional (in range on every phase) and
 // only the add is selected, so the hoisted-load structure of the RES == 1 path is kept.
 // SMEM > 0 (the kernel's LDS bytes): with a.stage_out the output tile is staged in LDS and written back as
 // whole 16-byte-per-lane rows; a lane's accumulators otherwise hold 4 channels of one pixel, so every store
@@ -56,7 +56,7 @@ PDT_DEVICE int swz(int row) { return (row >> 1) & (CHUNKS - 1); }
 template <int DT, int EPI, int RES, int FN, int FM, int WN, int WM, int BN, int WAVES_M, int NW_, int SMEM = 0,
           bool PERM = false>
 PDT_DEVICE void conv_epilogue(const ConvFwdArgs& a, f32x4_t (&acc)[FN][FM], int64_t m0, int n0, int tile_m, int wn,
-                              int wm, int tid, int lane, char* smem) {
+                              int wm, int tid, int lane, char* smem, int ph) {
   using E = E16<DT>;
   const int fr = lane & 15, fq = lane >> 4;
   const int PQ = a.Pm * a.Qm;
@@ -135,7 +135,7 @@ PDT_DEVICE void conv_epilogue(const ConvFwdArgs& a, f32x4_t (&acc)[FN][FM], int6
   char* stg = smem + STG_OFF;
   const int srow0 = FULL ? wm * WM : 0;  // this wave's first row in the staging buffer
   constexpr bool RC = RES == 2;
-  const bool res_on = !RC || (int)blockIdx.y == a.res_phase;  // compact: this block's phase owns the residual
+  const bool res_on = !RC || ph == a.res_phase;  // compact: this block's phase owns the residual
   // write the staged rows of wave row-group g (PERGRP) or of the whole tile (FULL) back: 16 B per lane, whole
   // BN-channel rows per pixel
   auto copy_rows = [&](int g) {
@@ -357,7 +357,7 @@ PDT_DEVICE void conv_epilogue(const ConvFwdArgs& a, f32x4_t (&acc)[FN][FM], int6
       for (int w = 0; w < WAVES_M; ++w)
 #pragma unroll
         for (int k = 0; k < KS; ++k) t[k] += red[(w * BN + tid) * KS + k];
-      const int64_t row = (a.nphase > 0 ? (int64_t)blockIdx.y * a.srows_pp : 0) + tile_m;
+      const int64_t row = (a.nphase > 0 ? (int64_t)ph * a.srows_pp : 0) + tile_m;
       const int64_t sld = a.nslice > 1 ? (int64_t)a.nslice * a.Kout : a.Kout;
       float* dst = a.srows + (row * sld + a.srows_coff + n0 + tid) * KO;
       if constexpr (EPI == 4)
@@ -368,16 +368,16 @@ PDT_DEVICE void conv_epilogue(const ConvFwdArgs& a, f32x4_t (&acc)[FN][FM], int6
   }
 }
 
-// Multi-phase launches size the grid for the largest phase; a block beyond its phase's tiles writes zeros
-// into the statistics row slice it owns (row = phase * srows_pp + M tile), so the fixed-order row reduction
-// never reads unwritten memory.
+// Multi-phase launches size the grid for the largest phase; grid slot ``slot`` of phase ``ph`` beyond the phase's
+// tiles writes zeros into the statistics row slice it owns (row = phase * srows_pp + M tile), so the fixed-order
+// row reduction never reads unwritten memory.
 template <int EPI, int BN_>
-PDT_DEVICE void zero_stat_row(const ConvFwdArgs& a, int nthreads) {
+PDT_DEVICE void zero_stat_row(const ConvFwdArgs& a, int nthreads, int slot, int ph) {
   if constexpr (EPI != 0) {
     constexpr int KO = EPI == 4 ? 4 : 2;
-    const int tm = (int)blockIdx.x / a.n_tiles, tn = (int)blockIdx.x - tm * a.n_tiles;
+    const int tm = slot / a.n_tiles, tn = slot - tm * a.n_tiles;
     const int64_t sld = a.nslice > 1 ? (int64_t)a.nslice * a.Kout : a.Kout;
-    float* dst = a.srows + (((int64_t)blockIdx.y * a.srows_pp + tm) * sld + a.srows_coff) * KO + (int64_t)tn * BN_ * KO;
+    float* dst = a.srows + (((int64_t)ph * a.srows_pp + tm) * sld + a.srows_coff) * KO + (int64_t)tn * BN_ * KO;
     for (int i = threadIdx.x; i < BN_ * KO; i += nthreads) dst[i] = 0.f;
   }
 }
@@ -402,7 +402,7 @@ void conv_fwd_kernel(ConvFwdArgs args) {
     a.srows_coff = sl * a.Kout;
   }
   if (args.nphase > 0 && !select_phase(a, args, wbase, blockIdx.y)) {  // multi-phase launch: this block's phase
-    zero_stat_row<EPI, BN>(a, NW * 64);
+    zero_stat_row<EPI, BN>(a, NW * 64, (int)blockIdx.x, (int)blockIdx.y);
     return;
   }
   using E = E16<DT>;
@@ -593,7 +593,7 @@ void conv_fwd_kernel(ConvFwdArgs args) {
   }
 
   conv_epilogue<DT, EPI, RES, FN, FM, WN, WM, BN, WAVES_M, NW, STAGES * STAGE, PERM>(a, acc, m0, n0, tile_m, wn, wm, tid,
-                                                                             lane, smem);
+                                                                             lane, smem, (int)blockIdx.y);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -625,13 +625,25 @@ PDT_DEVICE void vm_wait() {
   __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
 }
 
-template <int DT, int BM, int BN, int EPI, int RES, bool PP_STAGE = (EPI != 2)>  // (EPI 2 + staging spills)
+//
+// PERSISTENT: the launch is a 1-D grid of at most one workgroup per CU (launch_pp), and workgroup b walks the
+// work items b, b + G, b + 2G, ... of the (phase, grid slot) space the one-tile-per-workgroup grid used to cover
+// (item = phase * slots + slot, slots = srows_pp * n_tiles; a slot beyond its phase's tiles only zeroes the
+// statistics row it owns).  A tile's output and its partial statistics row depend on the item alone, never on the
+// workgroup that ran it, so every grid size gives the same bits.  With G a multiple of 8 a workgroup's items keep
+// its XCD's residue, so xcd_remap still hands each XCD a contiguous run of tiles (shared weight rows in its L2).
+// Before a tile's epilogue the DMA of the NEXT item's K-step 0 (all four pieces) is issued into the LDS buffer
+// the finished tile used least recently -- the other one than buffer (par + ksteps - 1) & 1 of its last K-step --
+// and the epilogue's scratch (statistics rows, BN coefficients) sits at the start of the buffer that last K-step
+// used, which nothing refills before the next tile's first barrier.  The next tile then runs its K loop with the
+// buffer parity carried over (``par``), its prologue (address set-up, cold first DMA) hidden under the epilogue.
+// The epilogue's stores are drained (vmcnt(0)) at the end of every tile: the statistics reduction's barriers
+// drain them anyway, and a partial tile issues a lane-dependent number of stores, so no counted wait is provable.
+// The tile split is static; there is no dynamic (ticket) claiming.
+// PDT_PP_PERSIST=0 sizes the grid to the item count (one tile per workgroup, no prefetch: the old schedule).
+// Measurements: profiles/pp_persistent_mi355x.md.
+template <int DT, int BM, int BN, int EPI, int RES>
 __global__ __launch_bounds__(512) void conv_pp_kernel(ConvFwdArgs args) {
-  ConvFwdArgs a = args;
-  if (args.nphase > 0 && !select_phase(a, args, args.w, blockIdx.y)) {  // strided backward-data: this block's phase
-    zero_stat_row<EPI, BN>(a, 512);
-    return;
-  }
   using E = E16<DT>;
   typedef typename E::vec8 vec8;
   constexpr int NW = 8, WN = 64, WM = 128;
@@ -654,78 +666,99 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvFwdArgs args) {
   const int grp = wave >> 2;  // waves w and w+4 share a SIMD: they run one barrier apart
   const int wn = wave % WAVES_N, wm = wave / WAVES_N;
 
-  const int nwg = a.m_tiles * a.n_tiles;
-  const int bid = xcd_remap(blockIdx.x, nwg);
-  const int tile_m = bid / a.n_tiles, tile_n = bid % a.n_tiles;
-  const int64_t m0 = (int64_t)tile_m * BM;
-  const int n0 = tile_n * BN;
+  // work items: (phase, grid slot) pairs in the order the one-tile-per-workgroup grid dispatched them
+  const int G = (int)gridDim.x;
+  const int slots = args.srows_pp * args.n_tiles;
+  const int total = (args.nphase > 0 ? args.nphase : 1) * slots;
+  // item -> its phase and slot, the phase's geometry into g (a copy of args); whether the slot is one of its tiles
+  auto decode = [&](ConvFwdArgs& g, int item, int& ph, int& slot) {
+    ph = 0;
+    slot = item;
+    if (args.nphase > 0) {
+      ph = (item >= slots) + (item >= 2 * slots) + (item >= 3 * slots);  // nphase <= 4
+      slot = item - ph * slots;
+      select_phase(g, args, args.w, ph);
+    }
+    return slot < g.m_tiles * g.n_tiles;
+  };
+  auto ksteps_of = [](const ConvFwdArgs& g) { return g.T * g.U * (g.C >> 6); };
 
-  const int PQ = a.Pm * a.Qm;
-  const FastDiv fd_pq{a.pq_mul, a.pq_shift}, fd_q{a.q_mul, a.q_shift};
-  const int TU = a.T * a.U;
-  const int csteps = a.C >> 6;
-  const int ksteps = TU * csteps;
-
-  const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, (uint32_t)a.N * a.H * a.W * a.cs * 2u);
-  const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.w, (uint32_t)a.Kout * TU * a.C * 2u);
+  const __amdgpu_buffer_rsrc_t rx = make_rsrc(args.x, (uint32_t)args.N * args.H * args.W * args.cs * 2u);
+  __amdgpu_buffer_rsrc_t rw = make_rsrc(args.w, 0u);
 
   // DMA lane geometry: 8 rows x 8 chunks of 16 B per 1 KiB instruction; the source chunk is XOR
   // swizzled by the LDS row so the ds_read_b128 fragment reads are conflict free
-  const int lrow = lane >> 3, pchunk = lane & 7;
+  // (the lane-derived DMA and fragment-read indices are recomputed per tile from an opaque copy of the lane id, so
+  // that they are dead, not loop-invariant registers, while the epilogue runs)
+  int lrow = 0, pchunk = 0;
   // X rows: packed (h << 16 | w & 0xffff) input position and byte offset, per half and instruction
   int xhw[2][NX], xoff[2][NX];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      const int hr = (wave * NX + j) * 8 + lrow;  // row of the half image
-      const int64_t m = m0 + (hr >> 6) * 128 + h * 64 + (hr & 63);
-      const int bch = pchunk ^ ((hr >> 1) & 7);
-      if (m < a.M) {
-        const int nimg = (int)fdiv((uint32_t)m, fd_pq);
-        const int rem = (int)m - nimg * PQ;
-        const int i = (int)fdiv((uint32_t)rem, fd_q), jj = rem - i * a.Qm;
-        const int ih = i * a.ist_h + a.ioff_h, iw = jj * a.ist_w + a.ioff_w;
-        xhw[h][j] = (ih << 16) | (iw & 0xffff);
-        xoff[h][j] = (((nimg * a.H + ih) * a.W + iw) * a.cs + bch * 8) * 2;
-      } else {
-        xhw[h][j] = (int)0xC0000000;  // h = -16384: always out of range
-        xoff[h][j] = 0;
-      }
-    }
   uint32_t woff[2][NWI];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int j = 0; j < NWI; ++j) {
-      const int hr = (wave * NWI + j) * 8 + lrow;
-      // permuted channel order inside each 32-row half (conv_epilogue PERM): LDS row f2*16 + m of the half holds
-      // channel (m >> 2)*8 + f2*4 + (m & 3) -- the row swizzle stays a function of the LDS row, conflict-free as before
-      const int lr = hr & 31;
-      const int n = n0 + (hr >> 5) * 64 + h * 32 + ((lr & 15) >> 2) * 8 + (lr >> 4) * 4 + (lr & 3);
-      woff[h][j] = (uint32_t)((n * TU * a.C + (pchunk ^ ((hr >> 1) & 7)) * 8) * 2);
-    }
-
-  // K-step cursor (tap, channel block) of the K-step whose DMA is being issued
-  int cur_t = 0, cur_u = 0, cur_c = 0;
+  // K-step cursor (tap, channel block) of the K-step whose DMA is being issued, over the U x C of the tile being
+  // loaded (ld_U: the phase of the tile whose DMA is issued may differ from the one in the epilogue)
+  int cur_t = 0, cur_u = 0, cur_c = 0, ld_U = 1;
   uint32_t s_adelta = 0;
   int s_dh = 0, s_dw = 0, s_bdelta = 0;
+  // DMA addresses of slot ``slot`` of g's phase; rewinds the K-step cursor
+  auto setup = [&](const ConvFwdArgs& g, int slot) {
+    const int bid = xcd_remap(slot, g.m_tiles * g.n_tiles);
+    const int tm = bid / g.n_tiles;
+    const int64_t m0 = (int64_t)tm * BM;
+    const int n0 = (bid - tm * g.n_tiles) * BN;
+    const int PQ = g.Pm * g.Qm;
+    const FastDiv fd_pq{g.pq_mul, g.pq_shift}, fd_q{g.q_mul, g.q_shift};
+    const int TU = g.T * g.U;
+    rw = make_rsrc(g.w, (uint32_t)g.Kout * TU * g.C * 2u);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int j = 0; j < NX; ++j) {
+        const int hr = (wave * NX + j) * 8 + lrow;  // row of the half image
+        const int64_t m = m0 + (hr >> 6) * 128 + h * 64 + (hr & 63);
+        const int bch = pchunk ^ ((hr >> 1) & 7);
+        if (m < g.M) {
+          const int nimg = (int)fdiv((uint32_t)m, fd_pq);
+          const int rem = (int)m - nimg * PQ;
+          const int i = (int)fdiv((uint32_t)rem, fd_q), jj = rem - i * g.Qm;
+          const int ih = i * g.ist_h + g.ioff_h, iw = jj * g.ist_w + g.ioff_w;
+          xhw[h][j] = (ih << 16) | (iw & 0xffff);
+          xoff[h][j] = (((nimg * g.H + ih) * g.W + iw) * g.cs + bch * 8) * 2;
+        } else {
+          xhw[h][j] = (int)0xC0000000;  // h = -16384: always out of range
+          xoff[h][j] = 0;
+        }
+      }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int j = 0; j < NWI; ++j) {
+        const int hr = (wave * NWI + j) * 8 + lrow;
+        // permuted channel order inside each 32-row half (conv_epilogue PERM): LDS row f2*16 + m of the half holds
+        // channel (m >> 2)*8 + f2*4 + (m & 3) -- the row swizzle stays a function of the LDS row, conflict-free as before
+        const int lr = hr & 31;
+        const int n = n0 + (hr >> 5) * 64 + h * 32 + ((lr & 15) >> 2) * 8 + (lr >> 4) * 4 + (lr & 3);
+        woff[h][j] = (uint32_t)((n * TU * g.C + (pchunk ^ ((hr >> 1) & 7)) * 8) * 2);
+      }
+    cur_t = 0; cur_u = 0; cur_c = 0;
+    ld_U = g.U;
+  };
+  // (H, W, C, cs and the tap steps are the same on every phase: read from args)
   auto advance = [&]() {  // latch the cursor's K-step deltas, then step the cursor
-    s_adelta = (uint32_t)((cur_t * a.U + cur_u) * a.C + cur_c) * 2u;
-    s_dh = cur_t * a.tstep_h;
-    s_dw = cur_u * a.tstep_w;
-    s_bdelta = ((s_dh * a.W + s_dw) * a.cs + cur_c) * 2;
+    s_adelta = (uint32_t)((cur_t * ld_U + cur_u) * args.C + cur_c) * 2u;
+    s_dh = cur_t * args.tstep_h;
+    s_dw = cur_u * args.tstep_w;
+    s_bdelta = ((s_dh * args.W + s_dw) * args.cs + cur_c) * 2;
     cur_c += 64;
-    if (cur_c == a.C) {
+    if (cur_c == args.C) {
       cur_c = 0;
-      if (++cur_u == a.U) { cur_u = 0; ++cur_t; }
+      if (++cur_u == ld_U) { cur_u = 0; ++cur_t; }
     }
   };
   auto dma_x = [&](char* buf, int h) {
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
       const int ih = (xhw[h][j] >> 16) + s_dh, iw = (int)(short)(xhw[h][j] & 0xffff) + s_dw;
-      const bool ok = (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
+      const bool ok = (unsigned)ih < (unsigned)args.H && (unsigned)iw < (unsigned)args.W;
       buf_lds16(rx, buf + (h ? OX1 : OX0) + (wave * NX + j) * 1024, ok ? (uint32_t)(xoff[h][j] + s_bdelta) : kOOB);
     }
   };
@@ -734,18 +767,19 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvFwdArgs args) {
     for (int j = 0; j < NWI; ++j)
       buf_lds16(rw, buf + (h ? OW1 : OW0) + (wave * NWI + j) * 1024, woff[h][j] + s_adelta);
   };
+  auto dma_step0 = [&](char* buf) {  // all of K-step 0 of the tile just set up
+    advance();
+    dma_x(buf, 0);
+    dma_w(buf, 0);
+    dma_w(buf, 1);
+    dma_x(buf, 1);
+  };
 
   f32x4_t acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const int fr = lane & 15, fq = lane >> 4;
   // fragment rows within the half images (the swizzle depends on the row only through bits 1..3,
   // which fr determines: every fragment base is a multiple of 16)
-  const int xrow0 = wm * 64 + fr, wrow0 = wn * 32 + fr;
-  const int sw = (fr >> 1) & 7;
+  int fq = 0, xrow0 = 0, wrow0 = 0, sw = 0;
   vec8 xs[4][2], w0r[2][2], w1r[2][2];
   auto read_x = [&](const char* base) {
 #pragma unroll
@@ -782,20 +816,54 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvFwdArgs args) {
     __builtin_amdgcn_sched_barrier(0);
   };
 
+  int par = 0;        // LDS buffer of the tile's K-step 0
+  bool have = false;  // the tile's K-step 0 is already in flight (issued before the previous tile's epilogue)
+  for (int item = (int)blockIdx.x; item < total; item += G) {
+    // The item is decoded, and its DMA addresses are computed, a second time here when its K-step 0 was prefetched:
+    // kept from the prefetch they would stay live across the epilogue, which has no registers to spare (its operand
+    // chunking is sized to the budget).  The opaque copy keeps the compiler from merging the two computations.
+    int item_o = item;
+    asm volatile("" : "+s"(item_o));
+    ConvFwdArgs a = args;
+    int ph = 0, slot = 0;
+    if (!decode(a, item_o, ph, slot)) {  // (never a prefetched item)
+      zero_stat_row<EPI, BN>(a, 512, slot, ph);
+      continue;
+    }
+    const int bid = xcd_remap(slot, a.m_tiles * a.n_tiles);
+    const int tile_m = bid / a.n_tiles, tile_n = bid - tile_m * a.n_tiles;
+    const int64_t m0 = (int64_t)tile_m * BM;
+    const int n0 = tile_n * BN;
+    const int ksteps = ksteps_of(a);
+    {
+      int lane_o = lane;
+      asm volatile("" : "+v"(lane_o));
+      const int fr = lane_o & 15;
+      lrow = lane_o >> 3; pchunk = lane_o & 7;
+      fq = lane_o >> 4; xrow0 = wm * 64 + fr; wrow0 = wn * 32 + fr;
+      sw = (fr >> 1) & 7;
+    }
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+      for (int j = 0; j < FM; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
   if (ksteps > 0) {
-    // prologue: all of K-step 0, then wait for its X0 / W0 (W1 and X1 may still fly)
-    advance();
-    dma_x(smem, 0);
-    dma_w(smem, 0);
-    dma_w(smem, 1);
-    dma_x(smem, 1);
-    vm_wait<NWI + NX>();
+    setup(a, slot);
+    if (!have) {
+      // cold prologue: all of K-step 0, then wait for its X0 / W0 (W1 and X1 may still fly)
+      dma_step0(smem + par * BUF);
+      vm_wait<NWI + NX>();
+    } else {
+      advance();     // K-step 0 is in flight: move the cursor past it
+      vm_wait<0>();  // the prefetched K-step 0 (already retired by the wait that ends every tile)
+    }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();  // stagger: waves 4-7 run one barrier behind
     for (int ks = 0; ks < ksteps; ++ks) {
-      const char* cb = smem + (ks & 1) * BUF;
-      char* nb = smem + ((ks + 1) & 1) * BUF;
+      const char* cb = smem + ((par + ks) & 1) * BUF;
+      char* nb = smem + ((par + ks + 1) & 1) * BUF;
       const bool more = ks + 1 < ksteps;
       if (more) advance();
       // phase 1: DMA X0(k+1); wait W1(k); read X0, W0; compute X0 x W0
@@ -819,9 +887,28 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvFwdArgs args) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
-
-  conv_epilogue<DT, EPI, RES, FN, FM, WN, WM, BN, WAVES_M, NW, PP_STAGE ? 2 * BUF : 0, true>(a, acc, m0, n0, tile_m, wn,
-                                                                                        wm, tid, lane, smem);
+    // every wave is past its last fragment read: the buffer of the last K-step takes the epilogue's scratch, the
+    // other one the next item's K-step 0 (read last in K-step ksteps - 2, or by the epilogue before this tile)
+    const int sb = ksteps > 0 ? (par + ksteps - 1) & 1 : par ^ 1;
+    have = false;
+    if (item + G < total) {
+      ConvFwdArgs an = args;
+      int nph = 0, nslot = 0;
+      if (decode(an, item + G, nph, nslot) && ksteps_of(an) > 0) {
+        setup(an, nslot);
+        dma_step0(smem + (sb ^ 1) * BUF);
+        have = true;
+      }
+    }
+    par = sb ^ 1;
+    // (no LDS-staged output: stage_out is 0 on this kernel, launch_pp)
+    conv_epilogue<DT, EPI, RES, FN, FM, WN, WM, BN, WAVES_M, NW, 0, true>(a, acc, m0, n0, tile_m, wn, wm, tid, lane,
+                                                                         smem + sb * BUF, ph);
+    // Retire the epilogue's operand loads and stores (and the prefetched K-step 0) here, where the compiler's wait
+    // insertion sees it on every path into the next tile: with an epilogue load still pending in its model at the
+    // K loop's header it put a vmcnt(0) in front of the loop's first register redefinition -- every K-step.
+    vm_wait<0>();
+  }
 }
 
 template <int DT, int BM, int BN>
@@ -834,7 +921,27 @@ static void launch_pp(const ConvFwdArgs& args, int gx, hipStream_t s) {
   if (a.nslice > 1)
     pdt_hip_fail("conv_pp: slice-batched (grouped) launches run on the generic kernel", hipErrorInvalidValue, __FILE__,
                  __LINE__);
-  dim3 grid(gx, a.nphase > 0 ? a.nphase : 1), block(512);
+  // persistent grid: at most one workgroup per CU (or ConvFwdArgs::max_wg) over the (phase, slot) items.
+  // PDT_PP_PERSIST (A/B only): bit 0 forward, bit 1 backward-data; a cleared bit sizes that role's grid to the item
+  // count -- one tile per workgroup, no prefetch, the schedule before the kernel was persistent.  Default 3.
+  static const int persist = [] {
+    const char* e = getenv("PDT_PP_PERSIST");
+    return e && e[0] ? atoi(e) : 3;
+  }();
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 256;
+    return n > 0 ? n : 256;
+  }();
+  const int total = gx * (a.nphase > 0 ? a.nphase : 1);
+  int G = total;
+  if (a.max_wg > 0)
+    G = a.max_wg;
+  else if (persist & (a.nphase > 0 ? 2 : 1))
+    G = cus;
+  if (G > total) G = total;
+  dim3 grid(G), block(512);
   const int rs = a.res == nullptr ? 0 : (a.res_phase >= 0 && a.nphase > 0 ? 2 : 1);
   const int epi = a.bnb ? a.bnb + 1 : (a.stats != nullptr ? 1 : 0);
 #define PDT_K(E_, R_) hipLaunchKernelGGL((conv_pp_kernel<DT, BM, BN, E_, R_>), grid, block, 0, s, a)

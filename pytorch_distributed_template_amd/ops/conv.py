@@ -81,9 +81,11 @@ def out_hw(H: int, W: int, R: int, S: int, stride: int, pad: int) -> Tuple[int, 
 
 
 def conv_fwd(x: torch.Tensor, w: torch.Tensor, stride: int = 1, pad: int = 0, stats: bool = False,
-             residual: Optional[torch.Tensor] = None, tile: Optional[Tuple[int, int, int]] = None):
+             residual: Optional[torch.Tensor] = None, tile: Optional[Tuple[int, int, int]] = None,
+             max_wg: int = 0):
     """y = conv(x, w) in NHWC/KRSC.  Returns ``y`` or ``(y, (sum, sumsq) per channel)`` with stats.
-    ``tile`` = (BM, BN, BK) overrides the per-shape table (tests / sweeps)."""
+    ``tile`` = (BM, BN, BK) overrides the per-shape table (tests / sweeps).  ``max_wg`` caps the workgroups of the
+    persistent ping-pong kernel (0: one per CU); the results do not depend on it."""
     N, H, W, C = x.shape
     K, R, S, C2 = w.shape
     assert C == C2
@@ -97,7 +99,7 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, stride: int = 1, pad: int = 0, st
     if stats:
         sp = torch.empty(native.C.stat_slots() * K * 2, dtype=torch.float64, device=x.device)
     native.C.conv_fwd(x, w, y, residual, sp, N, H, W, C, K, R, S, P, Q, stride, stride, -pad, -pad, 1, 1,
-                      P, Q, 1, 1, 0, 0, bm, bn, bk, 0)
+                      P, Q, 1, 1, 0, 0, bm, bn, bk, 0, max_wg)
     if not stats:
         return y
     sums = torch.empty(2 * K, dtype=torch.float64, device=x.device)
@@ -115,14 +117,15 @@ def pack_relu_mask(out: torch.Tensor) -> torch.Tensor:
 
 def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, H: int, W: int, stride: int = 1, pad: int = 0,
                residual: Optional[torch.Tensor] = None, bnb: Optional[tuple] = None,
-               tile: Optional[Tuple[int, int, int]] = None, res_phase: int = -1) -> torch.Tensor:
+               tile: Optional[Tuple[int, int, int]] = None, res_phase: int = -1, max_wg: int = 0) -> torch.Tensor:
     """dX (NHWC, [N, H, W, Cin]) of ``y = conv(x, w)`` given dY ([N, P, Q, Cout]).
 
     ``bnb = (mode, y1, coef1, y2, coef2, out_mask, slots)`` fuses the consuming BatchNorm's backward
     reduce into the epilogue (the result is then dz = dX * relu'; sums land in ``slots``); ``out_mask`` is
     the block output's ReLU bitmask (:func:`pack_relu_mask`, modes 2/3).  ``res_phase >= 0``: ``residual`` is
     compact ([N, ceil(H/stride), ceil(W/stride), Cin]) and added on that sub-pixel phase only (index into the
-    phases kept for this launch), e.g. a 1x1/2 downsample's data gradient added to a 3x3/2 one."""
+    phases kept for this launch), e.g. a 1x1/2 downsample's data gradient added to a 3x3/2 one.  ``max_wg``: as
+    :func:`conv_fwd`."""
     N, P, Q, K = dy.shape
     K2, R, S, C = w.shape
     assert K == K2
@@ -142,11 +145,11 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, H: int, W: int, stride: int = 
         phases.append([ph, pw, len(rs), len(ss), ioff_h, ioff_w, off])
         off += idx.numel()
     wt = torch.cat(pieces).contiguous() if pieces else torch.zeros(1, dtype=w.dtype, device=w.device)
-    if bnb is None and res_phase < 0:
+    if bnb is None and res_phase < 0 and max_wg == 0:
         native.C.conv_dgrad(dy, wt, dx, residual, N, P, Q, K, C, H, W, stride, phases, bm, bn, bk)
     else:
         native.C.conv_dgrad_bn(dy, wt, dx, residual, N, P, Q, K, C, H, W, stride, phases, bm, bn, bk,
-                               *(bnb or (0, None, None, None, None, None, None)), res_phase)
+                               *(bnb or (0, None, None, None, None, None, None)), res_phase, max_wg)
     return dx
 
 
