@@ -15,6 +15,36 @@ roundoff of fp32, i.e. one rounded fp32 operation on a value v is off by at most
   (first order); the products feeding the chain and the final fp32 -> fp64 partial sums add a few more ``u``: the model
   uses ``(n_chain + 4) * u * sum|term|``.
 
+Convolutions on the MFMA units (16-bit operands, fp32 accumulator), ``U = u = 2**-24``:
+
+* The product of two bf16 values (8 significand bits each) or two fp16 values (11 each) has at most 22 significand
+  bits: it is exact in fp32 (fp16 products below 2**-126 do not occur: the smallest non-zero fp16 product is 2**-48).
+* Every accumulation into the fp32 accumulator -- one product, a block of products the MFMA has summed internally, a
+  split-K partial, a row of ``wgrad_reduce`` -- errs by at most one fp32 ulp of the partial sum it produces, whatever
+  rounding mode the unit uses (round-to-nearest would give half of that; the mode for 16-bit inputs is not documented,
+  so the model takes the full ulp: ``2u`` relative instead of ``u``).  Every partial sum is bounded in magnitude by
+  ``mag``, the same operation applied to the absolute values of the operands.
+* A sum of ``n`` terms evaluated in any order and grouping passes through at most ``n - 1`` such accumulations per term
+  path, so to first order it is off by at most ``(n - 1) * 2u * mag``; the model uses ``(n + 4) * 2u * mag``, the five
+  extra accumulations covering the second-order terms (``n * 2u < 2**-9`` for every n here) and the residual add.
+* The 16-bit output rounds the fp32 value once: ``half_ulp16(ref, dtype)`` more.  A residual is added in fp32 before
+  that rounding: it is one more term, so ``|residual|`` joins ``mag``.
+* Forward and data gradient: ``|out - ref| <= half_ulp16(ref) + (n + 4) * 2u * mag`` with ``n = C*R*S`` (forward) or
+  ``Kout * taps of the phase`` (data gradient; ``Kout*R*S`` is a valid upper bound and the one used).
+* Weight gradient (fp32 output): ``|dw - ref| <= (n + 4) * 2u * mag``, ``n = N*P*Q``.
+* Forward statistics are sums of the ROUNDED outputs (and of their squares, each square one fp32 rounding): they are
+  judged with ``assert_sum`` (``n_chain = rows``) against fp64 sums of the stored ``y``; ``y`` itself is held by the
+  element bound.
+* Fused BN-backward sums are judged against the independent reference ``dz_ref``, never against the kernel's own
+  ``dz``: with ``bound_i`` the element bound of ``dz_i``,
+  ``|sum dz_k*xhat - sum dz_ref*xhat| <= sum_i bound_i*|xhat_i| + (rows + 4)*u*sum|dz_ref*xhat|`` (the first term is
+  the elements' own error carried into the sum, the second the fp32 chain: ``xhat = (y - mean) * invstd`` is two
+  roundings, the product one, all inside the ``+ 4`` and the margin of ``rows`` over the real chain length).  The same
+  with ``xhat = 1`` for ``sum dz``.  ``xhat`` is taken in fp64 from the fp32 ``mean`` / ``invstd`` the kernel reads.
+* Integer operands (``conv_int_operands``): every product and partial sum is an integer far below 2**24, so the fp32
+  accumulator is exact in any order; the result is ``ref64`` rounded once to the 16-bit type, bit for bit
+  (``assert_exact``: a zero bound).
+
 References are fp64 and are computed from the very 16-bit / fp32 values the kernel reads, so no input rounding enters
 the bounds.  ``tests/test_numerics_model_cpu.py`` proves that a plain fp32 evaluation of every formula stays inside its
 bound and that each assertion rejects a one-ulp error, a dropped row and coefficients shifted by one channel.
@@ -27,6 +57,7 @@ import json
 import os
 
 import torch
+import torch.nn.functional as F
 
 U = 2.0 ** -24
 
@@ -55,8 +86,9 @@ def half_ulp16(ref64: torch.Tensor, dtype) -> torch.Tensor:
     raise ValueError(f"no error model for {dtype}")
 
 
-def assert_within(got, ref64, bound64, name="value", C=None, family=None) -> float:
-    """|got - ref| <= bound for every element; the message names the worst element, its channel, error and bound."""
+def assert_within(got, ref64, bound64, name="value", C=None, family=None, shape=None) -> float:
+    """|got - ref| <= bound for every element; the message names the worst element, its channel, error and bound (and,
+    with ``shape``, its index in a tensor of that shape, e.g. (n, h, w, channel))."""
     got64 = got.detach().to(torch.float64).reshape(-1)
     ref = ref64.detach().to(torch.float64).reshape(-1)
     bound = bound64.detach().to(torch.float64).expand(ref64.shape).reshape(-1) if torch.is_tensor(bound64) \
@@ -72,6 +104,8 @@ def assert_within(got, ref64, bound64, name="value", C=None, family=None) -> flo
         i = int(ratio.argmax().item())
         nbad = int((ratio > 1.0).sum().item())
         ch = f", channel {i % C}" if C else ""
+        if shape is not None:
+            ch += f", index {tuple(int(v) for v in torch.unravel_index(torch.tensor(i), tuple(shape)))}"
         raise AssertionError(
             f"{name}: {nbad} of {ratio.numel()} elements out of bound; worst element {i}{ch}: got {got64[i].item()!r}, "
             f"ref {ref[i].item()!r}, error {err[i].item():.6e}, bound {bound[i].item():.6e} (ratio {worst:.3f})")
@@ -210,3 +244,159 @@ def sgd_ref(p, g, buf, wd_mask, lr, momentum, wd, gs, steps):
         acc += p64.abs() + lr * b.abs()
         p64 = p64 - lr * b
     return p64, b64, 6 * U * acc
+
+
+# ------------------------------------------------------------------------------------- convolutions (NHWC / KRSC)
+def _out_hw(H, W, R, S, stride, pad):
+    return (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+
+
+def _unfold_matmul(x64, wmat64, R, S, stride, pad):
+    """x64 [N, C, H, W], wmat64 [K, C*R*S] -> [N, K, L] (float64 im2col + matmul, the same code on CPU and GPU)."""
+    return torch.matmul(wmat64, F.unfold(x64, (R, S), padding=pad, stride=stride))
+
+
+def conv_fwd_ref(x, w, stride, pad, residual=None):
+    """fp64 y = conv(x, w) (+ residual) of NHWC ``x`` [N, H, W, C] and KRSC ``w`` [K, R, S, C] -> (ref, mag), both
+    [N, P, Q, K]; ``mag`` is the same operation on the absolute values of the operands."""
+    N, H, W, C = x.shape
+    K, R, S, _ = w.shape
+    P, Q = _out_hw(H, W, R, S, stride, pad)
+    x64 = x.to(torch.float64).permute(0, 3, 1, 2)
+    wm = w.to(torch.float64).permute(0, 3, 1, 2).reshape(K, C * R * S)
+    ref = _unfold_matmul(x64, wm, R, S, stride, pad).view(N, K, P, Q).permute(0, 2, 3, 1).contiguous()
+    mag = _unfold_matmul(x64.abs(), wm.abs(), R, S, stride, pad).view(N, K, P, Q).permute(0, 2, 3, 1).contiguous()
+    if residual is not None:
+        r64 = residual.to(torch.float64).view_as(ref)
+        ref, mag = ref + r64, mag + r64.abs()
+    return ref, mag
+
+
+def dgrad_as_correlation(dy, w, H, W, stride, pad, ftype):
+    """The data gradient as a stride-1 correlation: (zero-dilated, zero-padded dY [N, K, H+R-1, W+S-1], weight matrix
+    [C, K*R*S] with wt[c][k][r][s] = w[k][R-1-r][S-1-s][c]) in float type ``ftype``."""
+    N, P, Q, K = dy.shape
+    K2, R, S, C = w.shape
+    assert K == K2
+    top, left = R - 1 - pad, S - 1 - pad
+    Hd, Wd = H + R - 1, W + S - 1  # a stride-1 R x S window over this extent gives H x W outputs
+    assert top >= 0 and left >= 0
+    # dY rows beyond the extent would only meet inputs the forward conv never read
+    assert top + (P - 1) * stride < Hd and left + (Q - 1) * stride < Wd, "dY exceeds the forward geometry"
+    dil = torch.zeros(N, K, Hd, Wd, dtype=ftype, device=dy.device)
+    dil[:, :, top:top + (P - 1) * stride + 1:stride, left:left + (Q - 1) * stride + 1:stride] = \
+        dy.to(ftype).permute(0, 3, 1, 2)
+    return dil, w.to(ftype).flip(1, 2).permute(3, 0, 1, 2).reshape(C, K * R * S)
+
+
+def conv_dgrad_ref(dy, w, H, W, stride, pad, residual=None, res_phase=None):
+    """fp64 dX [N, H, W, C] of y = conv(x, w) given dY [N, P, Q, K] and KRSC ``w`` -> (ref, mag): the stride-1
+    correlation of the zero-dilated, zero-padded dY with the flipped, transposed weight.  ``residual`` has dX's shape,
+    or, with ``res_phase = (ph, pw)``, is compact [N, ceil((H-ph)/stride), ceil((W-pw)/stride), C] and is added on the
+    pixels (ph + stride*i, pw + stride*j) only."""
+    N, P, Q, K = dy.shape
+    R, S, C = w.shape[1:]
+    dil, wm = dgrad_as_correlation(dy, w, H, W, stride, pad, torch.float64)
+    ref = _unfold_matmul(dil, wm, R, S, 1, 0).view(N, C, H, W).permute(0, 2, 3, 1).contiguous()
+    mag = _unfold_matmul(dil.abs(), wm.abs(), R, S, 1, 0).view(N, C, H, W).permute(0, 2, 3, 1).contiguous()
+    if residual is not None:
+        r64 = residual.to(torch.float64)
+        if res_phase is not None:
+            ph, pw = res_phase
+            full = torch.zeros_like(ref)
+            full[:, ph::stride, pw::stride] = r64.view(N, -(-(H - ph) // stride), -(-(W - pw) // stride), C)
+            r64 = full
+        r64 = r64.view_as(ref)
+        ref, mag = ref + r64, mag + r64.abs()
+    return ref, mag
+
+
+def conv_wgrad_ref(x, dy, R, S, stride, pad):
+    """fp64 dW [K, R, S, C] of y = conv(x, w) from NHWC ``x`` and dY [N, P, Q, K] -> (ref, mag)."""
+    N, H, W, C = x.shape
+    _, P, Q, K = dy.shape
+    assert (P, Q) == _out_hw(H, W, R, S, stride, pad)
+    x64 = x.to(torch.float64).permute(0, 3, 1, 2)
+    d64 = dy.to(torch.float64).reshape(N, P * Q, K)
+
+    def one(xa, da):
+        cols = F.unfold(xa, (R, S), padding=pad, stride=stride)  # [N, C*R*S, L]
+        dw = torch.matmul(cols, da).sum(0)  # [C*R*S, K]
+        return dw.view(C, R, S, K).permute(3, 1, 2, 0).contiguous()
+    return one(x64, d64), one(x64.abs(), d64.abs())
+
+
+def conv_int_operands(shape, values, seed):
+    """A float32 CPU tensor of ``shape`` drawn uniformly from the integers ``values`` (CPU generator: the CPU test and
+    the GPU test see the same numbers)."""
+    g = torch.Generator().manual_seed(seed)
+    v = torch.tensor(values, dtype=torch.float32)
+    return v[torch.randint(len(values), tuple(shape), generator=g)]
+
+
+INT_RANGE = {torch.bfloat16: 256.0, torch.float16: 2048.0}  # |integer| up to here is exactly representable
+
+
+def int_case_conditions(ref64, dtype, K):
+    """The layer-A conditions on a reference alone: (share of outputs outside the exactly representable integer range of
+    ``dtype``, largest per-channel sum of squares of the rounded outputs)."""
+    share = float((ref64.abs() > INT_RANGE[dtype]).double().mean().item())
+    y = ref64.to(torch.float32).to(dtype).to(torch.float64).reshape(-1, K)
+    return share, float((y * y).sum(0).max().item())
+
+
+def conv_bound(ref64, mag64, n, dtype):
+    """Element bound of a 16-bit conv output (dtype float32: of an fp32 one): half_ulp16(ref) + (n + 4)*2u*mag."""
+    return half_ulp16(ref64, dtype) + (n + 4) * 2 * U * mag64.abs()
+
+
+def assert_conv(out, ref64, mag64, n, dtype, name, family):
+    """Every element of a forward / data-gradient (16-bit) or weight-gradient (``dtype`` float32) result within
+    ``conv_bound``; the failure names the element's index (n, h, w, channel)."""
+    return assert_within(out, ref64, conv_bound(ref64, mag64, n, dtype), name, ref64.shape[-1], family, ref64.shape)
+
+
+def assert_exact(out, expect, name):
+    """Layer A: ``out`` equals ``expect`` (fp64 integers already rounded to the output type) in every element; the
+    failure names the element, its index and the got / expected values."""
+    assert out.shape == expect.shape, f"{name}: shapes {tuple(out.shape)} {tuple(expect.shape)}"
+    return assert_within(out, expect, 0.0, name, expect.shape[-1], None, expect.shape)
+
+
+def round_exact(ref64, dtype):
+    """The one rounding layer A allows: fp64 integers -> fp32 (exact) -> the output type, back in fp64."""
+    return ref64.to(torch.float32).to(dtype).to(torch.float64)
+
+
+def assert_conv_stats(s, ss, y, name, family="conv16_stats", exact=False):
+    """Forward statistics against fp64 sums of the kernel's stored ``y`` [..., K]: the reduction alone (chain bound with
+    n_chain = rows; ``exact``: equal)."""
+    K = y.shape[-1]
+    y64 = y.to(torch.float64).reshape(-1, K)
+    rows = y64.shape[0]
+    r0, r1 = y64.sum(0), (y64 * y64).sum(0)
+    if exact:
+        return max(assert_within(s, r0, 0.0, f"{name}: sum", K), assert_within(ss, r1, 0.0, f"{name}: sumsq", K))
+    return max(assert_sum(s, r0, y64.abs().sum(0), rows, f"{name}: sum", K, family),
+               assert_sum(ss, r1, r1, rows, f"{name}: sumsq", K, family))
+
+
+def bn_xhat(y, coef, C):
+    """fp64 xhat = (y - mean) * invstd from the fp32 coefficients [scale | shift | mean | invstd] the kernel reads."""
+    c64 = coef.to(torch.float64)
+    return (y.to(torch.float64).reshape(-1, C) - c64[2 * C:3 * C]) * c64[3 * C:4 * C]
+
+
+def assert_bnb_sums(got_dz, got_dzx, dz_ref64, bound64, xhat64, name, family="conv16_bnb_sums", exact=False):
+    """Fused BN-backward sums against the independent reference: ``dz_ref64`` [rows, C] (masked fp64 data gradient;
+    ``exact``: already rounded to the output type), ``bound64`` the element bound of dz (zero where masked)."""
+    rows, C = dz_ref64.shape
+    t = dz_ref64 * xhat64
+    r0, r1 = dz_ref64.sum(0), t.sum(0)
+    if exact:
+        return max(assert_within(got_dz, r0, 0.0, f"{name}: sum dz", C),
+                   assert_within(got_dzx, r1, 0.0, f"{name}: sum dz*xhat", C))
+    b0 = bound64.sum(0) + (rows + 4) * U * dz_ref64.abs().sum(0)
+    b1 = (bound64 * xhat64.abs()).sum(0) + (rows + 4) * U * t.abs().sum(0)
+    return max(assert_within(got_dz, r0, b0, f"{name}: sum dz", C, family),
+               assert_within(got_dzx, r1, b1, f"{name}: sum dz*xhat", C, family))

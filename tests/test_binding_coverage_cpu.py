@@ -13,8 +13,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # name -> why no test calls it directly; queries, aliases and probes only
 ALLOWED_UNCALLED = {
     "conv_m_tiles": "query: the M-tile count of a conv plan, read by the executor's planner",
-    "conv_dgrad_bn": "alias: the conv_dgrad implementation with the BN-backward arguments spelled out; tests reach it "
-                     "through ops.conv.conv_dgrad(bnb=...)",
     "gconv_slice": "query: the grouped-conv channel-slice constant",
     "wgrad_3x3c64_supported": "query: shape predicate of the 3x3 C=64 wgrad kernel",
     "conv_dgrad_persistent": "query: which dgrad shapes take the persistent kernel",

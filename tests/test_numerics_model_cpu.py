@@ -221,3 +221,405 @@ def test_backward_reference_formula_equals_autograd_fp64():
     coef = torch.cat([A, beta.detach() - mean * A, mean, invstd])
     r = nm.bn_bwd_finalize_ref(sdz, sdzx, float(rows), coef, gamma.detach(), 1.0, C)
     assert (r["A"] * dz + r["B"] * yd + r["Cc"] - y.grad).abs().max().item() < 1e-10
+
+
+# =================================================================================== the conv error model (16-bit MFMA)
+# The reference alone; two correct fp32 implementations inside the bounds; ten mutations of a correct result, each on
+# ONE element (at a ragged-tail row and at an image-corner pixel), rejected by the assertion that owns them.
+import _conv_cases as cc  # noqa: E402
+
+
+def _ref_of(kind, g, dtype, layer, opt):
+    if kind == "fwd":
+        x, w, _ = cc.fwd_operands(g, dtype, layer, narrow=g in cc.NARROW)
+        return nm.conv_fwd_ref(x, w, g[6], g[7]) + (g[4],)
+    if kind == "fwd_pre":
+        z, w, _ = cc.fwd_operands(g, dtype, layer)
+        a = cc.pre_apply_ref(z, cc.pre_operands(layer, dtype), dtype).float().to(dtype)
+        return nm.conv_fwd_ref(a, w, g[6], g[7]) + (g[4],)
+    if kind == "stem":
+        x, wk = cc.stem_operands(g[0], g[1], g[2], dtype, layer)
+        return nm.conv_fwd_ref(x.to(dtype).permute(0, 2, 3, 1), wk, 2, 3) + (64,)
+    if kind.startswith("grouped"):
+        _, _, full = cc.grouped_weights(g[3], opt["groups"], dtype, layer)
+        if kind == "grouped_fwd":
+            return nm.conv_fwd_ref(cc.fwd_operands(g, dtype, layer)[0], full, g[6], g[7]) + (g[4],)
+        return nm.conv_dgrad_ref(cc.dgrad_operands(g, dtype, layer)[0], full, g[1], g[2], g[6], g[7]) + (g[3],)
+    dy, w, res = cc.dgrad_operands(g, dtype, layer, opt["residual"], narrow=g in cc.NARROW)
+    return nm.conv_dgrad_ref(dy, w, g[1], g[2], g[6], g[7], res, (0, 0) if opt["residual"] == "compact" else None) \
+        + (g[3],)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("kind,g,opt", cc.layer_a_cases(), ids=lambda v: str(v).replace(" ", ""))
+def test_layer_a_cases_stay_exactly_representable(kind, g, opt, dtype):
+    """At most 1 % of a case's outputs outside the dtype's exact integer range, every per-channel sum of squares below
+    2**24 (the statistics stay exact), and mag -- the bound on every partial sum -- below 2**24 (so does the
+    accumulator)."""
+    ref, mag, K = _ref_of(kind, g, dtype, "int", opt)
+    share, sumsq = nm.int_case_conditions(ref, dtype, K)
+    assert share <= 0.01, share
+    assert sumsq < 2.0 ** 24, sumsq
+    assert float(mag.max()) < 2.0 ** 24
+    assert bool((ref == ref.round()).all()) and bool((ref != 0).any())
+
+
+def test_layer_a_plain_fp32_conv_is_exact():
+    g = (2, 15, 13, 64, 128, 3, 2, 1)
+    x, w, _ = cc.fwd_operands(g, torch.bfloat16, "int")
+    ref, _ = nm.conv_fwd_ref(x, w, 2, 1)
+    y = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), stride=2, padding=1).permute(0, 2, 3, 1)
+    assert torch.equal(y.double(), ref)
+    dy, w, res = cc.dgrad_operands(g, torch.bfloat16, "int", "compact")
+    refd, _ = nm.conv_dgrad_ref(dy, w, 15, 13, 2, 1, res, (0, 0))
+    dx = torch.nn.grad.conv2d_input((2, 64, 15, 13), w.float().permute(0, 3, 1, 2), dy.float().permute(0, 3, 1, 2),
+                                    stride=2, padding=1).permute(0, 2, 3, 1).clone()
+    dx[:, ::2, ::2] += res.float()
+    assert torch.equal(dx.double(), refd)
+    xw, dyw = cc.wgrad_operands(g, torch.bfloat16, "int")
+    refw, _ = nm.conv_wgrad_ref(xw, dyw, 3, 3, 2, 1)
+    dw = torch.nn.grad.conv2d_weight(xw.float().permute(0, 3, 1, 2), (128, 64, 3, 3), dyw.float().permute(0, 3, 1, 2),
+                                     stride=2, padding=1).permute(0, 2, 3, 1)
+    assert torch.equal(dw.double(), refw)
+
+
+def _grouped_sum(a, b, dim_terms, chunk=32, splits=3):
+    """fp32 a @ b with the reduction axis evaluated adversarially: 32-term chunks summed first, the chunks of a split
+    accumulated in reverse order, the split-K partials summed last (in reverse as well)."""
+    T = dim_terms
+    edges = list(range(0, T, chunk)) + [T]
+    chunks = list(zip(edges[:-1], edges[1:]))
+    per = -(-len(chunks) // splits)
+    parts = []
+    for s0 in range(0, len(chunks), per):
+        acc = None
+        for lo, hi in reversed(chunks[s0:s0 + per]):
+            p = torch.matmul(a[..., lo:hi], b[..., lo:hi, :])
+            acc = p if acc is None else acc + p
+        parts.append(acc)
+    total = parts[-1]
+    for p in reversed(parts[:-1]):
+        total = total + p
+    return total
+
+
+EMUL_GEOMS = cc.DEFAULT_GEOMS[:5] + [cc.PP_GEOMS[2], cc.c64_geom(421)]
+
+
+def _record(family, worst, dtype):
+    key = f"{family}/{str(dtype).split('.')[-1]}"
+    nm.RATIOS[key] = max(nm.RATIOS.get(key, 0.0), worst)
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("g", EMUL_GEOMS, ids=str)
+def test_fp32_emulations_of_the_convs_stay_within_the_bounds(g, dtype):
+    """Plain torch fp32 conv / conv2d_input / conv2d_weight and the adversarially grouped fp32 evaluation, on the
+    layer-B operands: inside the bounds, ratios recorded (families cpu_*)."""
+    N, H, W, C, K, R, st, pad = g
+    P, Q = cc.out_hw(g)
+    nchw = lambda t: t.float().permute(0, 3, 1, 2)
+    # forward (+ residual, added in fp32 before the rounding)
+    x, w, res = cc.fwd_operands(g, dtype, "real", residual=True)
+    ref, mag = nm.conv_fwd_ref(x, w, st, pad, res)
+    plain = F.conv2d(nchw(x), nchw(w), stride=st, padding=pad).permute(0, 2, 3, 1) + res.float()
+    _record("cpu_plain_conv16_fwd",
+            nm.assert_conv(plain.to(dtype), ref, mag, C * R * R, dtype, "plain fwd", None), dtype)
+    cols = F.unfold(nchw(x), (R, R), padding=pad, stride=st)
+    wm = nchw(w).reshape(K, C * R * R)
+    grp = _grouped_sum(wm, cols, C * R * R).view(N, K, P, Q).permute(0, 2, 3, 1) + res.float()
+    _record("cpu_grouped_conv16_fwd",
+            nm.assert_conv(grp.to(dtype), ref, mag, C * R * R, dtype, "grouped fwd", None), dtype)
+    if dtype == torch.float16:
+        assert float(ref[..., 1].abs().max()) < 0.05  # the small channel
+    # statistics of the rounded outputs, fp32 chain
+    y = plain.to(dtype)
+    yf = y.float().reshape(-1, K)
+    s, ss = torch.zeros(K), torch.zeros(K)
+    for r in range(yf.shape[0]):
+        s, ss = s + yf[r], ss + yf[r] * yf[r]
+    _record("cpu_plain_conv16_stats", nm.assert_conv_stats(s, ss, y, "stats chain", family=None), dtype)
+    # data gradient
+    dy, w, res = cc.dgrad_operands(g, dtype, "real", "full")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+    plain = torch.nn.grad.conv2d_input((N, C, H, W), nchw(w), nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1) \
+        + res.float()
+    _record("cpu_plain_conv16_dgrad",
+            nm.assert_conv(plain.to(dtype), ref, mag, K * R * R, dtype, "plain dgrad", None), dtype)
+    dil, wt = nm.dgrad_as_correlation(dy, w, H, W, st, pad, torch.float32)
+    grp = _grouped_sum(wt, F.unfold(dil, (R, R)), K * R * R).view(N, C, H, W).permute(0, 2, 3, 1) + res.float()
+    _record("cpu_grouped_conv16_dgrad",
+            nm.assert_conv(grp.to(dtype), ref, mag, K * R * R, dtype, "grouped dgrad", None), dtype)
+    # weight gradient
+    x, dy = cc.wgrad_operands(g, dtype, "real")
+    ref, mag = nm.conv_wgrad_ref(x, dy, R, R, st, pad)
+    plain = torch.nn.grad.conv2d_weight(nchw(x), (K, C, R, R), nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1)
+    _record("cpu_plain_conv16_wgrad",
+            nm.assert_conv(plain, ref, mag, N * P * Q, torch.float32, "plain wgrad", None), dtype)
+    cols = F.unfold(nchw(x), (R, R), padding=pad, stride=st).permute(1, 0, 2).reshape(C * R * R, N * P * Q)
+    grp = _grouped_sum(cols, dy.float().reshape(N * P * Q, K), N * P * Q)  # [C*R*R, K]
+    grp = grp.view(C, R, R, K).permute(3, 1, 2, 0)
+    _record("cpu_grouped_conv16_wgrad",
+            nm.assert_conv(grp, ref, mag, N * P * Q, torch.float32, "grouped wgrad", None), dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("mode", [1, 2, 3])
+def test_fp32_emulation_of_the_fused_bn_backward_sums_stays_within_the_bound(mode, dtype):
+    g = (2, 14, 14, 64, 64, 3, 1, 1)
+    N, H, W, C, K, R, st, pad = g
+    dy, w, res = cc.dgrad_operands(g, dtype, "real", None if mode == 1 else "full")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+    d = cc.bnb_operands(mode, (N, H, W, C), dtype, "real")
+    mask, unsure = cc.bnb_mask(mode, d, C)
+    assert float(unsure.double().mean()) <= 1e-3
+    plain = torch.nn.grad.conv2d_input((N, C, H, W), w.float().permute(0, 3, 1, 2), dy.float().permute(0, 3, 1, 2),
+                                       stride=st, padding=pad).permute(0, 2, 3, 1)
+    if res is not None:
+        plain = plain + res.float()
+    if mode == 1:
+        m32 = (d["y1"].float().view(-1, C) * d["coef1"][:C] + d["coef1"][C:2 * C]) > 0
+    else:
+        m32 = mask
+    dz = torch.where(m32, plain.reshape(-1, C), torch.zeros(())).to(dtype)
+    ref2 = torch.where(mask, ref.reshape(-1, C), torch.zeros((), dtype=torch.float64))
+    full = nm.conv_bound(ref, mag, K * R * R, dtype).reshape(-1, C)
+    bound = torch.where(mask, full, torch.zeros_like(full))
+    sb = torch.where(unsure, ref.reshape(-1, C).abs() + full, bound)
+    for k in (1, 2) if mode == 3 else (1,):
+        yk, ck = d[f"y{k}"], d[f"coef{k}"]
+        xh32 = (yk.float().view(-1, C) - ck[2 * C:3 * C]) * ck[3 * C:]
+        s0, s1 = torch.zeros(C), torch.zeros(C)
+        for r in range(dz.shape[0]):
+            s0, s1 = s0 + dz[r].float(), s1 + dz[r].float() * xh32[r]
+        worst = nm.assert_bnb_sums(s0, s1, ref2, sb, nm.bn_xhat(yk, ck, C), f"branch {k}", family=None)
+        _record("cpu_plain_conv16_bnb_sums", worst, dtype)
+
+
+# ---- mutations
+def _terms(x, w, n, p, q, k, st, pad):
+    """fp64 products [C, R, S] of output element (n, p, q, k) (zero where the tap is padding)."""
+    _, H, W, C = x.shape
+    _, R, S, _ = w.shape
+    t = torch.zeros(C, R, S, dtype=torch.float64)
+    xin = torch.zeros(C, R, S, dtype=torch.float64)
+    for r in range(R):
+        for s in range(S):
+            h, ww = p * st - pad + r, q * st - pad + s
+            if 0 <= h < H and 0 <= ww < W:
+                xin[:, r, s] = x[n, h, ww].double()
+                t[:, r, s] = xin[:, r, s] * w[k, r, s].double()
+    return t, xin
+
+
+def _round16(v, dtype):
+    return torch.tensor(v, dtype=torch.float64).float().to(dtype)
+
+
+def _positions(ref, N, P, Q):
+    """(ragged-tail row, image-corner pixel): the last-but-one pixel row of the GEMM and pixel (0, 0, 0); the channel is
+    the one of median |ref| at that pixel: an ordinary element, inside every exact integer range and not one of the
+    few whose terms cancel (there the accumulation term of the bound outweighs a 16-bit ulp, rightly)."""
+    out = []
+    for (n, p, q) in ((N - 1, P - 1, Q - 2), (0, 0, 0)):
+        a = ref[n, p, q].abs()
+        k = int((a - a.median()).abs().argmin())
+        out.append((n, p, q, k))
+    return out
+
+
+def _expect_reject(layer, out, ref, mag, n_red, dtype):
+    with pytest.raises(AssertionError, match="out of bound"):
+        if layer == "int":
+            nm.assert_exact(out, nm.round_exact(ref, dtype), "mutated")
+        else:
+            nm.assert_conv(out, ref, mag, n_red, dtype, "mutated", None)
+
+
+def _accept(layer, out, ref, mag, n_red, dtype):
+    if layer == "int":
+        nm.assert_exact(out, nm.round_exact(ref, dtype), "correct")
+    else:
+        nm.assert_conv(out, ref, mag, n_red, dtype, "correct", None)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_element_assertions_reject_a_dropped_tap_channel_and_a_neighbouring_channel(layer, dtype):
+    """Mutations 1-3 on one element of a 3x3 64 -> 64 forward."""
+    g = (2, 14, 14, 64, 64, 3, 1, 1)
+    N, H, W, C, K, R, st, pad = g
+    x, w, _ = cc.fwd_operands(g, dtype, layer)
+    ref, mag = nm.conv_fwd_ref(x, w, st, pad)
+    good = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), padding=pad).permute(0, 2, 3, 1)
+    good = good.to(dtype)
+    _accept(layer, good, ref, mag, C * 9, dtype)
+    for (n, p, q, k) in _positions(ref, N, H, W):
+        t, xin = _terms(x, w, n, p, q, k, st, pad)
+        assert abs(float(t.sum()) - float(ref[n, p, q, k])) < 1e-9
+        drop_tap = t.clone()
+        drop_tap[:, 1, 1] = 0  # the centre tap is inside the image at every pixel
+        # (integer terms can cancel: take the first channel whose contribution, or whose exchange, is not zero)
+        c0 = next(c for c in range(5, C) if float(t[c].sum()) != 0)
+        drop_ch = t.clone()
+        drop_ch[c0] = 0
+        c1 = next(c for c in range(5, C - 1) if float((xin[c + 1] * w[k, :, :, c].double() - t[c]).sum()) != 0)
+        neigh = t.clone()
+        neigh[c1] = xin[c1 + 1] * w[k, :, :, c1].double()
+        for m in (drop_tap, drop_ch, neigh):
+            bad = good.clone()
+            bad[n, p, q, k] = _round16(float(m.sum()), dtype)
+            _expect_reject(layer, bad, ref, mag, C * 9, dtype)
+
+
+def _step_ulp(t16, away_from):
+    """The neighbouring representable value of the one-element 16-bit tensor on the side away from ``away_from``."""
+    bits = t16.clone().view(torch.int16)
+    up, down = (bits + 1).view(t16.dtype), (bits - 1).view(t16.dtype)
+    return up if abs(float(up) - away_from) > abs(float(down) - away_from) else down
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_element_assertions_reject_one_ulp_and_truncation_at_64_terms(layer, dtype):
+    """Mutations 4 and 5 on the 64-term 1x1 conv, where the half-ulp term dominates the bound."""
+    g = (2, 12, 12, 64, 256, 1, 1, 0)
+    N, H, W, C, K, R, st, pad = g
+    x, w, _ = cc.fwd_operands(g, dtype, layer)
+    ref, mag = nm.conv_fwd_ref(x, w, st, pad)
+    acc = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+    good = acc.to(dtype)
+    _accept(layer, good, ref, mag, C, dtype)
+    for (n, p, q, k) in _positions(ref, N, H, W):
+        bad = good.clone()
+        bad[n, p, q, k] = _step_ulp(good[n, p, q, k].reshape(1), float(ref[n, p, q, k]))[0]
+        _expect_reject(layer, bad, ref, mag, C, dtype)
+        if layer == "int":
+            continue  # (integers are exact: there is nothing to truncate)
+        # truncation: the 16-bit value next towards zero wherever rounding to nearest went away from zero
+        row = good[n, p, q]
+        went_up = row.double().abs() > acc[n, p, q].double().abs()
+        bits = row.clone().view(torch.int16)
+        trunc = torch.where(went_up, bits - 1, bits).view(dtype)  # sign-magnitude: -1 on the bits is towards zero
+        bound = nm.conv_bound(ref[n, p, q], mag[n, p, q], C, dtype)
+        ratio = (trunc.double() - ref[n, p, q]).abs() / bound
+        kk = int(ratio.argmax())
+        assert float(ratio[kk]) > 1.0
+        bad = good.clone()
+        bad[n, p, q, kk] = trunc[kk]
+        _expect_reject(layer, bad, ref, mag, C, dtype)
+    if layer == "real":  # and truncation everywhere
+        bits = good.clone().view(torch.int16)
+        trunc = torch.where(good.double().abs() > acc.double().abs(), bits - 1, bits).view(dtype)
+        _expect_reject(layer, trunc, ref, mag, C, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_element_assertions_reject_a_doubled_and_a_misplaced_residual(layer, dtype):
+    """Mutations 6 and 7 on a strided data gradient."""
+    g = (2, 15, 13, 64, 128, 3, 2, 1)
+    N, H, W, C, K, R, st, pad = g
+    nchw = lambda t: t.float().permute(0, 3, 1, 2)
+    dy, w, res = cc.dgrad_operands(g, dtype, layer, "full")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+    plain = torch.nn.grad.conv2d_input((N, C, H, W), nchw(w), nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1)
+    good = (plain + res.float()).to(dtype)
+    _accept(layer, good, ref, mag, K * 9, dtype)
+    for (n, p, q, k) in _positions(ref, N, H, W):
+        bad = good.clone()
+        bad[n, p, q, k] = (plain[n, p, q, k] + 2 * res[n, p, q, k].float()).to(dtype)
+        _expect_reject(layer, bad, ref, mag, K * 9, dtype)
+    # compact residual of phase (0, 0) placed on phase (0, 1) instead: one element of the wrong tensor
+    dy, w, rc = cc.dgrad_operands(g, dtype, layer, "compact")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, rc, (0, 0))
+    good = plain.clone()
+    good[:, ::2, ::2] += rc.float()
+    good = good.to(dtype)
+    _accept(layer, good, ref, mag, K * 9, dtype)
+    wrong = plain.clone()
+    wrong[:, ::2, 1::2] += rc.float()[:, :, :W // 2]
+    wrong = wrong.to(dtype)
+    for (n, p, q) in ((N - 1, H - 1, W - 1), (0, 0, 0), (0, 0, 1)):  # two pixels that lose it, one that gains it
+        bad = good.clone()
+        bad[n, p, q, 7] = wrong[n, p, q, 7]
+        _expect_reject(layer, bad, ref, mag, K * 9, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_statistics_assertion_rejects_one_missing_row(layer, dtype):
+    """Mutation 8."""
+    g = (2, 14, 14, 64, 64, 3, 1, 1)
+    x, w, _ = cc.fwd_operands(g, dtype, layer)
+    y = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1).to(dtype)
+    y64 = y.double().reshape(-1, 64)
+    s, ss = y64.sum(0), (y64 * y64).sum(0)
+    nm.assert_conv_stats(s, ss, y, "correct", family=None, exact=layer == "int")
+    for row in (y64.shape[0] - 2, 0):
+        with pytest.raises(AssertionError, match="out of bound"):
+            nm.assert_conv_stats(s - y64[row], ss, y, "sum", family=None, exact=layer == "int")
+        with pytest.raises(AssertionError, match="out of bound"):
+            nm.assert_conv_stats(s, ss - y64[row] ** 2, y, "sumsq", family=None, exact=layer == "int")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_bn_backward_sums_assertion_rejects_branch_1_coefficients_on_branch_2(layer, dtype):
+    """Mutation 9, and the sums of a dz that is wrong in one element (what a reference taken from the kernel's own
+    output could never see)."""
+    g = (2, 14, 14, 64, 64, 3, 1, 1)
+    N, H, W, C, K, R, st, pad = g
+    dy, w, res = cc.dgrad_operands(g, dtype, layer, "full")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+    d = cc.bnb_operands(3, (N, H, W, C), dtype, layer)
+    mask, _ = cc.bnb_mask(3, d, C)
+    ref2 = torch.where(mask, ref.reshape(-1, C), torch.zeros((), dtype=torch.float64))
+    full = nm.conv_bound(ref, mag, K * 9, dtype).reshape(-1, C)
+    bound = torch.where(mask, full, torch.zeros_like(full))
+    exact = layer == "int"
+    dz = nm.round_exact(ref2, dtype)  # a correct kernel's dz (correctly rounded)
+    x1, x2 = nm.bn_xhat(d["y1"], d["coef1"], C), nm.bn_xhat(d["y2"], d["coef2"], C)
+    want = dz if exact else ref2
+    nm.assert_bnb_sums(dz.sum(0), (dz * x2).sum(0), want, bound, x2, "correct", family=None, exact=exact)
+    with pytest.raises(AssertionError, match="out of bound"):
+        nm.assert_bnb_sums(dz.sum(0), (dz * x1).sum(0), want, bound, x2, "branch 2", family=None, exact=exact)
+    # y2 read with branch 1's mean / invstd
+    c12 = torch.cat([d["coef2"][:2 * C], d["coef1"][2 * C:]])
+    with pytest.raises(AssertionError, match="out of bound"):
+        nm.assert_bnb_sums(dz.sum(0), (dz * nm.bn_xhat(d["y2"], c12, C)).sum(0), want, bound, x2, "branch 2",
+                           family=None, exact=exact)
+    # one element of dz without one term, summed consistently: the exact layer sees it in the sums as well (in the
+    # real layer a single term is below the sums' bound and is the element assertion's to catch)
+    if not exact:
+        return
+    rows = dz.shape[0]
+    for row in (rows - 2, 0):
+        k = int(mask[row].double().argmax())
+        bad = dz.clone()
+        bad[row, k] = float(_round16(float(ref2[row, k] - dy[row // (H * W), (row // W) % H, row % W, 5].double()
+                                           * w[5, 1, 1, k].double()), dtype))
+        assert bad[row, k] != dz[row, k]
+        with pytest.raises(AssertionError, match="out of bound"):
+            nm.assert_bnb_sums(bad.sum(0), (bad * x1).sum(0), want, bound, x1, "branch 1", family=None, exact=exact)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_element_assertion_rejects_a_value_from_another_group_slice(layer, dtype):
+    """Mutation 10: one output of slice 0 holds slice 1's value at the same pixel."""
+    width, groups, stride, H = cc.GROUPED[0]
+    g = cc.grouped_geom(width, groups, stride, H)
+    _, _, full = cc.grouped_weights(width, groups, dtype, layer)
+    x, _, _ = cc.fwd_operands(g, dtype, layer)
+    ref, mag = nm.conv_fwd_ref(x, full, stride, 1)
+    good = F.conv2d(x.float().permute(0, 3, 1, 2), full.float().permute(0, 3, 1, 2), stride=stride,
+                    padding=1).permute(0, 2, 3, 1).to(dtype)
+    _accept(layer, good, ref, mag, 64 * 9, dtype)
+    P, Q = cc.out_hw(g)
+    for (n, p, q) in ((1, P - 1, Q - 2), (0, 0, 0)):
+        k = next(k for k in range(64) if good[n, p, q, k] != good[n, p, q, k + 64])
+        bad = good.clone()
+        bad[n, p, q, k] = good[n, p, q, k + 64]
+        _expect_reject(layer, bad, ref, mag, 64 * 9, dtype)
