@@ -466,7 +466,9 @@ void conv32_launch(Conv32Args a, int bm, int bn, hipStream_t s) {
   int gx = 0;
   const int srows = conv_geom_plan(a, bm, bn, &gx);
   if (gx == 0) return;
-  PDT_COUNT(a.nphase > 0 ? "conv32_dgrad" : "conv32_fwd");
+  // (PDT_COUNT binds its counter at the site's first execution: one literal name per site)
+  if (a.nphase > 0) PDT_COUNT("conv32_dgrad");
+  else PDT_COUNT("conv32_fwd");
   const int KO = a.bnb && a.bn_y2 ? 4 : 2;
   Scratch part(a.stats ? (size_t)srows * a.Kout * KO * sizeof(float) : 0, s);
   a.srows = part.as<float>();

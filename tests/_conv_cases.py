@@ -1,19 +1,24 @@
-"""The conv cases and operands shared by tests/test_conv_numerics_gpu.py (the kernels) and
-tests/test_numerics_model_cpu.py (the error model): one list, so the two cannot drift apart (a plain module).
+"""The conv cases and operands shared by tests/test_conv_numerics_gpu.py, tests/test_conv32_numerics_gpu.py (the
+kernels; the fp32 path's lists are at the end) and tests/test_numerics_model_cpu.py (the error model): one list, so they
+cannot drift apart (a plain module).
 
 A geometry is ``(N, H, W, C, K, R, stride, pad)``: NHWC input [N, H, W, C], KRSC weight [K, R, R, C].  Operands are
 made on the CPU generator and are the same numbers wherever they are used.
 
 Layer A (``layer="int"``): activations, gradients and residuals from {-2, -1, 1, 2}, weights from {-1, 1}: no zeros,
 so every dropped, doubled or misplaced term changes the integer result, and every partial sum is exact in fp32.
-Layer B (``layer="real"``): randn rounded to the dtype, weights scaled by (reduction length)**-0.5; fp16 cases scale
-one output channel by 1e-3 so its outputs approach the subnormal range.
+Layer B (``layer="real"``): randn rounded to the dtype, weights scaled by (reduction length)**-0.5; fp16 and fp32 cases
+scale one output channel by 1e-3 (fp16 outputs approach the subnormal range; a small channel cannot hide in a norm).
 """
 import torch
 
 import _numerics as nm
 
 DTYPES = [torch.bfloat16, torch.float16]
+F32 = torch.float32
+# layer B scales one output channel (and that channel of the residual) by 1e-3 for these dtypes: fp16 outputs approach
+# the subnormal range, and an fp32 channel of small magnitude cannot hide in a norm
+SMALL_CHANNEL = (torch.float16, torch.float32)
 XVALS = (-2, -1, 1, 2)
 WVALS = (-1, 1)
 
@@ -104,7 +109,7 @@ def fwd_operands(g, dtype, layer, narrow=False, residual=False):
     x = _real((N, H, W, C), gen, dtype)
     wf = torch.randn(K, R, R, C, generator=gen) * (1.0 / (C * R * R)) ** 0.5
     rf = torch.randn(N, P, Q, K, generator=gen) if residual else None
-    if dtype == torch.float16:
+    if dtype in SMALL_CHANNEL:
         wf[1] *= 1e-3
         if residual:
             rf[..., 1] *= 1e-3
@@ -131,7 +136,7 @@ def dgrad_operands(g, dtype, layer, residual=None, narrow=False):
     dy = _real((N, P, Q, K), gen, dtype)
     wf = torch.randn(K, R, R, C, generator=gen) * (1.0 / (K * R * R)) ** 0.5
     rf = torch.randn(*rshape, generator=gen) if rshape else None
-    if dtype == torch.float16:
+    if dtype in SMALL_CHANNEL:
         wf[..., 1] *= 1e-3
         if rf is not None:
             rf[..., 1] *= 1e-3
@@ -270,3 +275,219 @@ def layer_a_cases():
             seen.add(key)
             uniq.append((kind, g, opt))
     return uniq
+
+
+# ======================================================================================= the fp32 path (fp32.hip)
+# tests/test_conv32_numerics_gpu.py runs these on the kernels, tests/test_numerics_model_cpu.py proves the layer-A
+# conditions and the assertions on them.  Three layers: "int" and "real" as above (dtype float32), and "wide": 1x1
+# geometries whose every output is exactly one non-zero product that needs the full 24-bit multiply.
+C32_TILE_GEOM = (13, 13, 11, 128, 256, 3, 2, 1)      # M = 546: ragged on 128, 256 and 512 rows; dgrad GEMM-N = 128
+C32_TILE_GEOM_256 = (13, 13, 11, 256, 64, 3, 2, 1)   # dgrad GEMM-N = 256: the (256, 256) tile
+C32_TILES = [(128, 128), (128, 64), (256, 256), (256, 128), (256, 64), (512, 64)]
+C32_FWD_VARIANTS = ["plain", "res", "stats", "stats_res"]
+# backward-data epilogues: (name, bnb mode of bnb_operands or 0, residual); mode 2: one branch, stored mask reference;
+# mode 3: two branches (always a stored mask); mode 1: one branch, the mask recomputed from y1 (bn_mref = None)
+C32_EPILOGUES = [("none", 0, False), ("res", 0, True), ("bn1", 2, False), ("bn1_res", 2, True), ("bn2", 3, False),
+                 ("bn2_res", 3, True), ("bn1_nomref", 1, False)]
+C32_DEFAULT_GEOMS = [
+    (2, 14, 9, 64, 64, 3, 1, 1),
+    (2, 15, 13, 64, 128, 3, 2, 1),
+    (3, 14, 11, 128, 256, 1, 2, 0),  # dgrad: three phases without taps write zeros plus the residual
+    (2, 12, 7, 64, 256, 1, 1, 0),
+    (1, 9, 5, 96, 128, 3, 1, 1),     # C % 32 only
+    (2, 8, 6, 512, 128, 3, 1, 1),
+]
+# 3x3/s1/p1 on the halo kernel (bn = 64); the reduction has C channels and the output K, in both directions
+C32_HALO_GEOMS = [
+    (2, 8, 56, 64, 64, 3, 1, 1),    # W at the 464-row limit; tiles start mid-row and cross the image boundary
+    (3, 5, 64, 32, 64, 3, 1, 1),    # the isolated admitted width; one channel chunk
+    (30, 3, 3, 96, 128, 3, 1, 1),   # one tile spans 28 images; three chunks; two column tiles
+    (5, 10, 10, 64, 64, 3, 1, 1),
+    (3, 7, 9, 128, 128, 3, 1, 1),
+]
+C32_HALO_REFUSED = [(2, 8, 57, 64, 64, 3, 1, 1), (3, 5, 2, 64, 64, 3, 1, 1)]  # the restaging kernel must run
+W32_T64 = [(2, 9, 7, 64, 64, 3, 1, 1), (3, 6, 5, 64, 128, 3, 2, 1), (2, 7, 5, 192, 64, 1, 1, 0)]
+W32_T128 = [(3, 6, 5, 128, 128, 3, 2, 1), (1, 7, 6, 384, 128, 3, 1, 1)]
+W32_HALO = [(2, 5, 62, 64, 64, 3, 1, 1), (3, 9, 28, 64, 128, 3, 1, 1), (2, 6, 5, 128, 64, 3, 1, 1),
+            (2, 56, 56, 64, 64, 3, 1, 1)]
+# window-mode stem images (N, H, W); the last two carry an odd pooled width (9) / an odd conv width (19) and a
+# partial last 32-pixel chunk for the fused weight gradient
+STEM32 = [(3, 32, 24), (3, 64, 48)]
+STEM32_FUSED = STEM32 + [(3, 40, 36), (2, 42, 38)]
+STEM32_TILES = [(128, 64), (256, 64), (512, 64)]
+WIDE_VARIANTS = ["a", "b", "c"]
+WIDE_FWD = [(2, 9, 7, 32, 64, 1, 1, 0), (2, 9, 7, 64, 128, 1, 1, 0)]  # one and two K-steps; 126 pixels: a ragged tile
+WIDE_WGRAD = [((1, 8, 8, 64, 64, 1, 1, 0), 64), ((2, 8, 8, 128, 128, 1, 1, 0), 128)]  # N*P*Q == C; (geometry, tile)
+
+
+def dgrad_geom32(g):
+    """The geometry whose backward-data pass reduces over g's ``C`` channels and writes g's ``K``: the listed channel
+    counts name (reduction, output) in both directions, and conv32_dgrad needs its output channels % 64 == 0."""
+    N, H, W, C, K, R, st, pad = g
+    return (N, H, W, K, C, R, st, pad)
+
+
+def tile32_default(n, m):
+    """The tile ResNetExecutor32._tile32 chooses for a GEMM of n columns and m rows."""
+    from pytorch_distributed_template_amd.models.executor32 import ResNetExecutor32
+    return ResNetExecutor32._tile32(ResNetExecutor32, n, m)
+
+
+def dgrad_geoms32_default():
+    """C32_DEFAULT_GEOMS for backward data: as listed where the output channels allow a 64-wide tile, else swapped."""
+    return [g if g[3] % 64 == 0 else dgrad_geom32(g) for g in C32_DEFAULT_GEOMS]
+
+
+def wgrad32_plans(g, tile, target=1024):
+    """Split plans (splits, pix_per_split) of a weight gradient: one split; the plan ResNetExecutor32._wgrad makes for
+    ``target`` blocks; a plan whose last split is partial; for the halo tile one output row per split.  (A split that
+    owns no pixel at all is produced by no caller and is left out.)"""
+    N, H, W, C, K, R, st, pad = g
+    P, Q = out_hw(g)
+    plans = []
+    if tile == 3:
+        rows = N * P
+        per_split = 3 * (K // 64) * (C // 64)
+        s = max(1, min(target // per_split, rows))
+        pps = -(-rows // s)
+        part = next(p for p in range(2, rows + 2) if rows % p != 0 or p > rows)
+        for pp in (rows, pps, part, 1):
+            plans.append((-(-rows // pp), pp))
+    else:
+        npix = N * P * Q
+        per_split = (K // tile) * R * R * (C // tile)
+        tgt = target if tile == 64 else target // 2
+        s = max(1, min(tgt // max(per_split, 1), (npix + 63) // 64))
+        pps = (-(-npix // s) + 63) // 64 * 64
+        for pp in ((npix + 63) // 64 * 64, pps, 64):
+            plans.append((-(-npix // pp), pp))
+    return sorted(set(plans))
+
+
+def wide_pair(shape_act, shape_w, variant, seed):
+    """(activation-side, weight-side) fp32 operands of the ``wide`` layer: (a) 12-bit odd integers on both sides -- the
+    product needs 23 or 24 bits --, (b) 24-bit odd integers against +-{1, 2, 4}, (c) the mirror of (b)."""
+    if variant == "a":
+        return nm.wide_operand(shape_act, 12, seed), nm.wide_operand(shape_w, 12, seed + 1)
+    if variant == "b":
+        return nm.wide_operand(shape_act, 24, seed), nm.wide_small(shape_w, seed + 1)
+    return nm.wide_small(shape_act, seed), nm.wide_operand(shape_w, 24, seed + 1)
+
+
+def wide_fwd_operands(g, variant):
+    """(x, w) of a 1x1 forward (or, as (dy, w), of a 1x1 backward-data with g = dgrad_geom32(...)): the activation of
+    pixel p is non-zero only in channel (7 p) % C of its reduction channels."""
+    N, H, W, C, K, R, st, pad = g
+    assert R == 1 and st == 1 and pad == 0
+    a, w = wide_pair((N * H * W, C), (K, 1, 1, C), variant, _seed(g, 51))
+    p = torch.arange(N * H * W)
+    keep = torch.zeros(N * H * W, C)
+    keep[p, (7 * p) % C] = 1.0
+    return (a * keep).view(N, H, W, C).contiguous(), w
+
+
+def wide_dgrad_operands(g, variant):
+    """(dy [N, H, W, K], w [K, 1, 1, C]) of a 1x1 backward-data: dY of pixel p is non-zero only in channel (7 p) % K."""
+    N, H, W, C, K, R, st, pad = g
+    assert R == 1 and st == 1 and pad == 0
+    a, w = wide_pair((N * H * W, K), (K, 1, 1, C), variant, _seed(g, 52))
+    p = torch.arange(N * H * W)
+    keep = torch.zeros(N * H * W, K)
+    keep[p, (7 * p) % K] = 1.0
+    return (a * keep).view(N, H, W, K).contiguous(), w
+
+
+def wide_wgrad_operands(g, variant):
+    """(x, dy) of a 1x1 weight gradient over N*P*Q == C pixels: pixel p carries input channel (7 p) % C alone (7 and C
+    are coprime: every channel has exactly one pixel), so dW[k][c] is one product."""
+    N, H, W, C, K, R, st, pad = g
+    assert R == 1 and st == 1 and pad == 0 and N * H * W == C
+    x, dy = wide_pair((C, C), (C, K), variant, _seed(g, 53))
+    p = torch.arange(C)
+    keep = torch.zeros(C, C)
+    keep[p, (7 * p) % C] = 1.0
+    return (x * keep).view(N, H, W, C).contiguous(), dy.view(N, H, W, K).contiguous()
+
+
+def stem32_operands(N, H, W, layer):
+    """(fp32 NCHW image, KRSC 7x7 weight [64, 7, 7, 3], dY [N, P, Q, 64]) of the fp32 window-mode stem."""
+    P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    sd = 61 + H * W
+    if layer == "int":
+        return (nm.conv_int_operands((N, 3, H, W), XVALS, sd), nm.conv_int_operands((64, 7, 7, 3), WVALS, sd + 1),
+                nm.conv_int_operands((N, P, Q, 64), XVALS, sd + 2))
+    gen = torch.Generator().manual_seed(sd)
+    w = torch.randn(64, 7, 7, 3, generator=gen) / 147 ** 0.5
+    w[1] *= 1e-3
+    return torch.randn(N, 3, H, W, generator=gen), w, torch.randn(N, P, Q, 64, generator=gen)
+
+
+def stem32_tail_operands(N, P, Q, layer, C=64, seed=0):
+    """Operands of the stem's backward tail over the conv output [N, P, Q, C]: dict with y (conv output), dp (pooled
+    gradient [N, OH, OW, C]), idx (random argmax codes 0..8, codes that point outside the image included), coef
+    ([scale | shift | mean | invstd]) and b ([A | B | Cc]).  Layer A: integer y and dp, scale +-{1, 2, 4}, shift 0.5 (the
+    pre-activation is never zero), power-of-two A and B, integer Cc: dY = A*dz + B*y + Cc is exact."""
+    OH, OW = (P - 1) // 2 + 1, (Q - 1) // 2 + 1
+    gen = torch.Generator().manual_seed(71 + 13 * P + Q + C + seed)
+    idx = torch.randint(0, 9, (N, OH, OW, C), generator=gen, dtype=torch.uint8)
+    ch = torch.arange(C)
+    if layer == "int":
+        y = nm.conv_int_operands((N, P, Q, C), XVALS, 72 + P + seed)
+        dp = nm.conv_int_operands((N, OH, OW, C), XVALS, 73 + P + seed)
+        scale = torch.tensor([1.0, 2.0, 4.0])[ch % 3] * torch.where((ch // 3) % 2 == 0, 1.0, -1.0)
+        coef = torch.cat([scale, torch.full((C,), 0.5), ((ch % 3) - 1).float(),
+                          torch.tensor([0.25, 0.5, 1.0, 2.0])[(ch // 2) % 4]])
+        b = torch.cat([torch.tensor([1.0, 2.0, 0.5])[ch % 3] * torch.where((ch // 2) % 2 == 0, 1.0, -1.0),
+                       torch.tensor([2.0, -1.0, 1.0, -2.0])[ch % 4], ((ch % 5) - 2).float()])
+    else:
+        y = torch.randn(N, P, Q, C, generator=gen)
+        dp = torch.randn(N, OH, OW, C, generator=gen)
+        sign = torch.where(torch.rand(C, generator=gen) < 0.3, -1.0, 1.0)
+        coef = torch.cat([(torch.rand(C, generator=gen) + 0.5) * sign, torch.randn(C, generator=gen) * 0.3,
+                          torch.randn(C, generator=gen) * 0.3, torch.rand(C, generator=gen) + 0.5])
+        b = torch.cat([(torch.rand(C, generator=gen) + 0.5) * sign.roll(1), torch.randn(C, generator=gen) * 0.2,
+                       torch.randn(C, generator=gen) * 0.1])
+    return dict(y=y, dp=dp, idx=idx, coef=coef.contiguous(), b=b.contiguous())
+
+
+def stem_tail_ref(d, N, P, Q, C):
+    """Independent fp64 reference of the stem's backward tail from ``stem32_tail_operands`` (any device): the pooled
+    gradient scattered along the argmax bytes (codes pointing outside the image select nothing), the ReLU mask from
+    y*scale + shift, dY = A*dz + B*y + Cc.  Returns dict dz, dzmag (scatter of |dp|), unsure (|pre| <= 8u*mag: the sign
+    fp32 may call either way), dy, dymag (|A|*dzmag + |B*y| + |Cc|), dyflip (|A|*dzmag where unsure, else 0)."""
+    y, dp, idx = d["y"], d["dp"], d["idx"]
+    dev = y.device
+    OH, OW = (P - 1) // 2 + 1, (Q - 1) // 2 + 1
+    dz = torch.zeros(N, P, Q, C, dtype=torch.float64, device=dev)
+    dzmag = torch.zeros_like(dz)
+    n_i, oh_i, ow_i, c_i = torch.meshgrid(*[torch.arange(s, device=dev) for s in (N, OH, OW, C)], indexing="ij")
+    h = oh_i * 2 - 1 + (idx // 3).long()
+    w = ow_i * 2 - 1 + (idx % 3).long()
+    ok = (h >= 0) & (h < P) & (w >= 0) & (w < Q)
+    flat = ((n_i * P + h) * Q + w) * C + c_i
+    dz.view(-1).index_put_((flat[ok],), dp.double()[ok], accumulate=True)
+    dzmag.view(-1).index_put_((flat[ok],), dp.double().abs()[ok], accumulate=True)
+    c64 = d["coef"].double()
+    t1, t2 = y.double() * c64[:C], c64[C:2 * C]
+    pre = t1 + t2
+    unsure = pre.abs() <= 8 * nm.U * (t1.abs() + t2.abs())
+    dzraw = dz
+    dz = torch.where(pre > 0, dz, torch.zeros_like(dz))
+    b64 = d["b"].double()
+    A, B, Cc = b64[:C], b64[C:2 * C], b64[2 * C:3 * C]
+    dy = A * dz + B * y.double() + Cc
+    dymag = A.abs() * dzmag + (B * y.double()).abs() + Cc.abs()
+    dyflip = torch.where(unsure, A.abs() * dzmag, torch.zeros_like(dzmag))
+    return dict(dz=dz, dzraw=dzraw, dzmag=dzmag, unsure=unsure, dy=dy, dymag=dymag, dyflip=dyflip)
+
+
+def layer_a_cases32():
+    """Every fp32 layer-A case: (kind, geometry, options)."""
+    out = [("fwd", C32_TILE_GEOM, {"residual": True})]
+    out += [("dgrad", g, {"residual": "full"}) for g in (C32_TILE_GEOM, C32_TILE_GEOM_256)]
+    out += [("fwd", g, {"residual": True}) for g in C32_DEFAULT_GEOMS + C32_HALO_GEOMS + C32_HALO_REFUSED]
+    out += [("dgrad", g, {"residual": "full"}) for g in dgrad_geoms32_default()]
+    out += [("dgrad", dgrad_geom32(g), {"residual": "full"}) for g in C32_HALO_GEOMS + C32_HALO_REFUSED]
+    out += [("wgrad", g, {}) for g in W32_T64 + W32_T128 + W32_HALO]
+    out += [("stem", (N, H, W, 3, 64, 7, 2, 3), {}) for N, H, W in STEM32_FUSED]
+    return out

@@ -45,6 +45,32 @@ Convolutions on the MFMA units (16-bit operands, fp32 accumulator), ``U = u = 2*
   accumulator is exact in any order; the result is ``ref64`` rounded once to the 16-bit type, bit for bit
   (``assert_exact``: a zero bound).
 
+Convolutions on the fp32 MFMA (v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulator; csrc/kernels/fp32.hip):
+
+* The product of two fp32 values has up to 48 significand bits: unlike the 16-bit case it is NOT exact in fp32.  Whether
+  the unit rounds each product before adding it or fuses the multiply into the add, a term enters the accumulator with
+  at most one rounding of its own: ``2u * |x * w|`` under the same full-ulp convention as above.
+* The accumulation is the 16-bit model's: at most ``n - 1`` accumulations per term path, each off by at most one fp32
+  ulp of a partial sum bounded by ``mag``; split-K partials and ``wgrad_reduce`` rows are further accumulations of the
+  same kind.  Together with the product's rounding a term passes through at most ``n`` roundings:
+  ``n * 2u * mag`` to first order.  The model uses ``(n + 5) * 2u * mag``: the 16-bit model's ``n + 4`` plus the one
+  rounding per product; the five extra roundings cover the second-order terms (``n * 2u < 2**-10`` up to n = 8192) and
+  the residual add.  The output is stored as fp32: no further rounding, no ``half_ulp16`` term.
+* Forward and data gradient: ``|out - ref| <= (n + 5) * 2u * mag`` with ``n = C*R*S`` / ``Kout*R*S``; weight gradient
+  the same with ``n = N*P*Q`` (``conv32_bound``).  Statistics and fused BN-backward sums are judged exactly as in the
+  16-bit case (``assert_conv_stats`` family ``conv32_stats``, ``assert_bnb_sums`` family ``conv32_bnb_sums``).
+* Integer operands: every product and partial sum is an integer below 2**24 (checked per case from the reference:
+  ``max mag < 2**24`` and every per-channel sum of squares below 2**24), so output, statistics and fused sums EQUAL the
+  fp64 reference: there is no representability cap, fp32 holds every such integer.
+* The worst-case bound grows with n and says little about the width of the multiply at long reductions (operands rounded
+  to 8 bits still pass at n = 4608).  The ``wide`` layer owns that: every output is exactly ONE non-zero product whose
+  exact value needs 24 bits, or whose one operand does (``wide_operand``): a product or an operand kept to fewer bits
+  changes every element.
+* The fused stem weight gradient (``wgrad32_stem_fused``) forms dY = A*dz + B*y + C in the kernel (dz: up to 4 pooled
+  gradients added in fp32): each term of dY carries at most 3 + 4 roundings before it meets the product, one more than
+  half of the ``k = 8`` elementwise budget and 7 more than a stored operand: ``(n + 12) * 2u * mag`` with ``mag`` the
+  weight-gradient of ``|x|`` and ``|A|*sum|dp| + |B*y| + |C|``.
+
 References are fp64 and are computed from the very 16-bit / fp32 values the kernel reads, so no input rounding enters
 the bounds.  ``tests/test_numerics_model_cpu.py`` proves that a plain fp32 evaluation of every formula stays inside its
 bound and that each assertion rejects a one-ulp error, a dropped row and coefficients shifted by one channel.
@@ -334,7 +360,8 @@ def conv_int_operands(shape, values, seed):
     return v[torch.randint(len(values), tuple(shape), generator=g)]
 
 
-INT_RANGE = {torch.bfloat16: 256.0, torch.float16: 2048.0}  # |integer| up to here is exactly representable
+INT_RANGE = {torch.bfloat16: 256.0, torch.float16: 2048.0,  # |integer| up to here is exactly representable
+             torch.float32: 2.0 ** 24}
 
 
 def int_case_conditions(ref64, dtype, K):
@@ -354,6 +381,43 @@ def assert_conv(out, ref64, mag64, n, dtype, name, family):
     """Every element of a forward / data-gradient (16-bit) or weight-gradient (``dtype`` float32) result within
     ``conv_bound``; the failure names the element's index (n, h, w, channel)."""
     return assert_within(out, ref64, conv_bound(ref64, mag64, n, dtype), name, ref64.shape[-1], family, ref64.shape)
+
+
+def conv32_bound(mag64, n, extra=5):
+    """Element bound of an fp32 MFMA conv output: (n + 5)*2u*mag (``extra`` = 12: the fused stem weight gradient)."""
+    return (n + extra) * 2 * U * mag64.abs()
+
+
+def assert_conv32(out, ref64, mag64, n, name, family, extra=5):
+    """Every element of an fp32 forward / data-gradient / weight-gradient result within ``conv32_bound``."""
+    return assert_within(out, ref64, conv32_bound(mag64, n, extra), name, ref64.shape[-1], family, ref64.shape)
+
+
+def int32_case_conditions(ref64, mag64, K):
+    """The fp32 integer layer's conditions on a reference alone: (largest magnitude bound of a partial sum, largest
+    per-channel sum of squares of the outputs); both must stay below 2**24."""
+    y = ref64.reshape(-1, K)
+    return float(mag64.max().item()), float((y * y).sum(0).max().item())
+
+
+def wide_operand(shape, bits, seed):
+    """fp32 CPU tensor of random-sign odd integers with exactly ``bits`` significant bits (2**(bits-1)+1 ..
+    2**bits - 1): every bit of the significand field in use matters, the lowest included."""
+    g = torch.Generator().manual_seed(seed)
+    half = torch.randint(2 ** (bits - 2), 2 ** (bits - 1), tuple(shape), generator=g)  # 2*half + 1 is odd, top bit set
+    sign = torch.randint(0, 2, tuple(shape), generator=g) * 2 - 1
+    return ((2 * half + 1) * sign).to(torch.float32)
+
+
+def wide_small(shape, seed):
+    """fp32 CPU tensor from +-{1, 2, 4}: a product with it is exact and keeps every bit of the other operand."""
+    return conv_int_operands(shape, (-4, -2, -1, 1, 2, 4), seed)
+
+
+def round_to_bits(t, bits):
+    """``t`` (fp32) rounded to ``bits`` significand bits, to nearest even (the mutation of the ``wide`` proofs)."""
+    m, e = torch.frexp(t.double())
+    return torch.ldexp(torch.round(m * 2.0 ** bits) / 2.0 ** bits, e).float()
 
 
 def assert_exact(out, expect, name):

@@ -18,6 +18,10 @@ Worst observed error / bound on an MI355X with these seeds (information, not a t
 coefficients 0.50; 1b bn_apply 0.9999 (the half-ulp term is tight by construction: a correct rounding reaches it); 1c
 bn_bwd_reduce 0.013; 1d bn_bwd_finalize 0.50; 1e bn_bwd_apply 0.99999; 1f the chain in executor order 0.997 (its
 elementwise stages; dgamma / dbeta against autograd far below); 1g the fp32 family 0.32.
+
+1h, the fp32 stem tail (bn_relu_maxpool32, stem_pool_bwd_apply32, stem_pool_bwd_reduce32, stem_pack32): each against its
+own fp64 reference (window maximum, scatter of the pooled gradient along the argmax bytes + ReLU mask + A*dz + B*y + C,
+the sums of that dz, the bit pattern of the packed image), never against another kernel of this project.
 """
 import math
 
@@ -698,3 +702,135 @@ def test_maxpool_bwd_relu32(N, H, W, C):
     sure = val.abs() > 8 * U * (t1.abs() + t2.abs())
     assert bool(torch.isfinite(dz).all())
     nm.assert_sum(dz[sure], ref[sure], mag[sure], 4, "maxpool_bwd_relu32", family="1g")
+
+
+# ------------------------------------------------------------------------------------------------ 1h: the fp32 stem tail
+import _conv_cases as cc  # noqa: E402
+
+
+def _pool_windows(v_nhwc, fill):
+    """[N, H, W, C] fp64 -> [N, OH, OW, C, 9]: the 3x3 / stride 2 / pad 1 windows, positions outside the image = fill."""
+    N, H, W, C = v_nhwc.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    p = F.pad(v_nhwc.permute(0, 3, 1, 2), (1, 1, 1, 1), value=fill)
+    cols = F.unfold(p, (3, 3), stride=2).view(N, C, 9, OH, OW)
+    return cols.permute(0, 3, 4, 1, 2).contiguous()
+
+
+@pytest.mark.parametrize("N,H,W,C", [(2, 12, 11, 64), (2, 13, 11, 64), (3, 27, 27, 192), (2, 55, 55, 64), (2, 13, 11, 4)])
+def test_bn_relu_maxpool32(N, H, W, C):
+    """out within 8u * mag of the fp64 max(relu(y * scale + shift)) over the in-image window (mag: the largest
+    |y * scale| + |shift| of the window: the maximum of values each off by at most that is off by at most that); idx
+    names an in-image window position whose fp64 value is within the bound of the maximum (near-ties may go either
+    way).  Odd H / W: border windows of 4 and 6 members."""
+    torch.manual_seed(H * W + C)
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.randn(N, H, W, C, device=DEV)
+    coef = _coef4(C, tiny=False)
+    out, idx = _nan(N, OH, OW, C), torch.full((N, OH, OW, C), 255, dtype=torch.uint8, device=DEV)
+    _C().bn_relu_maxpool32(y, coef, out, idx, N, H, W, C)
+    c64 = coef.double()
+    t1, t2 = y.double() * c64[:C], c64[C:2 * C]
+    win = _pool_windows(torch.relu(t1 + t2), -1.0)
+    bound = 8 * U * _pool_windows(t1.abs() + t2.abs().expand_as(t1), 0.0).max(-1).values
+    ref = win.max(-1).values
+    nm.assert_within(out, ref, bound, "bn_relu_maxpool32: out", C, family="1h", shape=ref.shape)
+    assert bool((idx < 9).all()), "bn_relu_maxpool32: an argmax byte was not written or is not a window position"
+    chosen = win.gather(-1, idx.long().unsqueeze(-1)).squeeze(-1)
+    assert bool((chosen >= 0).all()), "bn_relu_maxpool32: idx names a position outside the image"
+    nm.assert_within(chosen, ref, bound, "bn_relu_maxpool32: value at idx", C, shape=ref.shape)
+
+
+@pytest.mark.parametrize("N,H,W,C", [(2, 13, 11, 64), (3, 9, 7, 4)])
+def test_bn_relu_maxpool32_decisive(N, H, W, C):
+    """Integer y whose 9 values differ inside every 3x3 window (a per-plane permutation of -4 .. 4 laid out by (h % 3,
+    w % 3)), power-of-two scale, shift 0.5: every window value is exact, a positive maximum is unique, and negative
+    values all clamp to 0 -- an all-negative window (planes c % 8 == 5 hold -9 .. -1 under a positive scale) gives
+    out == 0 at the first in-image position.  out and idx must match exactly."""
+    g = torch.Generator().manual_seed(H + C)
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    perm = (torch.argsort(torch.rand(N, C, 9, generator=g), dim=-1) - 4).float()
+    ch = torch.arange(C)
+    perm[:, ch % 8 == 5] -= 5.0
+    pos = (torch.arange(H).view(H, 1) % 3) * 3 + torch.arange(W).view(1, W) % 3
+    y = perm[:, :, pos].permute(0, 2, 3, 1).contiguous().to(DEV)
+    scale = torch.tensor([1.0, 2.0, 4.0])[ch % 3] * torch.where((ch // 3) % 2 == 0, 1.0, -1.0)
+    scale[ch % 8 == 5] = 2.0
+    coef = torch.cat([scale, torch.full((C,), 0.5), torch.zeros(2 * C)]).to(DEV)
+    out, idx = _nan(N, OH, OW, C), torch.full((N, OH, OW, C), 255, dtype=torch.uint8, device=DEV)
+    _C().bn_relu_maxpool32(y, coef, out, idx, N, H, W, C)
+    win = _pool_windows(torch.relu(y.double() * coef[:C].double() + 0.5), -1.0)
+    ref = win.max(-1)
+    assert bool((ref.values[..., ch % 8 == 5] == 0).all()) and bool((ref.values > 0).any())
+    nm.assert_within(out, ref.values, 0.0, "bn_relu_maxpool32 decisive: out", C, shape=ref.values.shape)
+    bad = (idx.long() != ref.indices).nonzero()
+    assert bad.numel() == 0, (f"bn_relu_maxpool32 decisive: {bad.shape[0]} argmax bytes differ; first at (n, oh, ow, c) = "
+                              f"{tuple(bad[0].tolist())}: got {int(idx[tuple(bad[0])])}, "
+                              f"expected {int(ref.indices[tuple(bad[0])])}")
+
+
+@pytest.mark.parametrize("N,H,W,C", [(2, 12, 11, 64), (2, 13, 11, 64), (2, 55, 55, 64), (2, 13, 11, 4)])
+def test_stem_pool_bwd_apply32(N, H, W, C):
+    """dy = A*dz + B*y + Cc with dz recomputed in the kernel, against the fp64 scatter + mask of cc.stem_tail_ref and
+    nm.bn_bwd_apply_ref's formula: (8 + 4) * u * mag -- the elementwise budget plus the up to 4 window gradients dz
+    collects in fp32.  Elements whose ReLU sign fp32 may call either way are not compared.  C = 4: cshift = 0."""
+    d = {k: v.to(DEV).contiguous() for k, v in cc.stem32_tail_operands(N, H, W, "real", C=C).items()}
+    r = cc.stem_tail_ref(d, N, H, W, C)
+    ref, mag = nm.bn_bwd_apply_ref(r["dz"], d["y"], d["b"], C)
+    assert float((ref.view_as(r["dy"]) - r["dy"]).abs().max()) == 0.0
+    dy = _nan(N, H, W, C)
+    _C().stem_pool_bwd_apply32(d["dp"].view(-1), d["idx"].view(-1), d["y"].view(-1), d["coef"], d["b"], dy.view(-1), N, H,
+                               W, C)
+    assert bool(torch.isfinite(dy).all())
+    sure = ~r["unsure"]
+    assert float(sure.double().mean()) > 0.99
+    nm.assert_within(dy[sure], r["dy"][sure], 12 * U * r["dymag"][sure], "stem_pool_bwd_apply32", family="1h")
+
+
+@pytest.mark.parametrize("N,H,W,C,blocks", [(2, 13, 11, 64, 1), (2, 13, 11, 64, 7), (2, 12, 11, 64, 7), (1, 3, 5, 64, 20),
+                                            (2, 13, 11, 4, 7)])
+def test_stem_pool_bwd_reduce32(N, H, W, C, blocks):
+    """sum dz and sum dz * xhat against the same fp64 dz: the chain bound of the kernel's lane plan (rpi = 256 / (C / 4)
+    row lanes, as test_bn_bwd_reduce32) with 4 more additions for the window gradients dz collects; a pixel whose ReLU
+    sign fp32 may call either way may contribute its gradient or nothing.  blocks = 20 exceeds the 15 pixel rows."""
+    C_ = _C()
+    S = C_.stat_slots()
+    d = {k: v.to(DEV).contiguous() for k, v in cc.stem32_tail_operands(N, H, W, "real", C=C, seed=blocks).items()}
+    r = cc.stem_tail_ref(d, N, H, W, C)
+    rows = N * H * W
+    slots = _nan(S * C * 2, dtype=torch.float64)
+    C_.reset_dispatch_counts()
+    C_.stem_pool_bwd_reduce32(d["dp"].view(-1), d["idx"].view(-1), d["y"].view(-1), d["coef"], slots, blocks, N, H, W, C)
+    torch.cuda.synchronize()
+    assert dict(C_.dispatch_counts()).get("stem_pool_bwd_fused32", 0) == 1
+    assert bool(torch.isfinite(slots).all())
+    got = slots.view(S, C, 2).sum(0)
+    xh = nm.bn_xhat(d["y"], d["coef"], C)
+    dz, dzmag = r["dz"].reshape(-1, C), r["dzmag"].reshape(-1, C)
+    flip = torch.where(r["unsure"].reshape(-1, C), dzmag, torch.zeros_like(dzmag))
+    rpi = 256 // (C // 4)
+    n_chain = math.ceil(rows / (blocks * rpi)) + rpi + 4
+    ref = torch.stack([dz.sum(0), (dz * xh).sum(0)], 1)
+    mag = torch.stack([dzmag.sum(0), (dzmag * xh.abs()).sum(0)], 1)
+    extra = torch.stack([flip.sum(0), (flip * xh.abs()).sum(0)], 1)
+    nm.assert_within(got, ref, (n_chain + 4) * U * mag + extra, f"stem_pool_bwd_reduce32 blocks={blocks}", 2, family="1h")
+
+
+@pytest.mark.parametrize("Cin", [1, 3])
+@pytest.mark.parametrize("N,H,W,extra", [(2, 9, 7, 0), (3, 32, 24, 2), (1, 5, 6, 5)])
+def test_stem_pack32(N, H, W, extra, Cin):
+    """The zero-padded NHWC4 image equals the NCHW input bit for bit at every interior pixel and is exactly zero in
+    the unused channels, in the border and in the extra rows and columns (Hp, Wp larger than H + 2 * pad)."""
+    torch.manual_seed(H + W + Cin)
+    pad = 3
+    Hp, Wp = H + 2 * pad + extra, W + 2 * pad + (extra + 1 if extra else 0)
+    x = torch.randn(N, Cin, H, W, device=DEV)
+    x[0, 0, 0, 0] = -0.0
+    out = _nan(N, Hp, Wp, 4)
+    _C().stem_pack32(x, out.view(-1), N, Cin, H, W, pad, Hp, Wp)
+    expect = torch.zeros(N, Hp, Wp, 4, device=DEV)
+    expect[:, pad:pad + H, pad:pad + W, :Cin] = x.permute(0, 2, 3, 1)
+    bad = (out.view(torch.int32) != expect.view(torch.int32)).nonzero()
+    assert bad.numel() == 0, (f"stem_pack32: {bad.shape[0]} elements differ; first at (n, hp, wp, c) = "
+                              f"{tuple(bad[0].tolist())}: got {float(out[tuple(bad[0])])!r}, "
+                              f"expected {float(expect[tuple(bad[0])])!r}")

@@ -1,6 +1,9 @@
 """The native fp32 path (reference precision: `distributed.py` / `dataparallel.py` train without autocast):
 fp32 MFMA conv forward / multi-phase backward-data / weight gradient vs PyTorch fp32 autograd, the fp32 executor's
-training step vs an fp32 torch model, and the entry script on --precision fp32 (MI355X)."""
+training step vs an fp32 torch model, and the entry script on --precision fp32 (MI355X).
+
+The per-element checks of these kernels against fp64 (every tile, epilogue, halo width, split plan and the window-mode
+stem) are tests/test_conv32_numerics_gpu.py and the stem-tail tests of tests/test_bn_chain_gpu.py."""
 import copy
 import os
 import subprocess
@@ -265,33 +268,6 @@ def test_fp32_syncbn_native_comm_world1_equals_plain_bn():
     assert _rel(out[0], out[1]) < 1e-5
 
 
-@pytest.mark.parametrize("tile", [(128, 64), (256, 64)])
-def test_conv32_stem_window_mode_matches_torch(tile):
-    """fp32 stem in window mode (conv32 over the zero-padded NHWC4 image: K = 7 kernel rows x (8 pixels x 4 channels),
-    no im2col buffer) vs torch's fp32 conv2d, with the BN statistics epilogue."""
-    from pytorch_distributed_template_amd.ops import native
-    C = native.C
-    torch.manual_seed(3)
-    N, H, W = 3, 64, 48
-    x = torch.randn(N, 3, H, W, device=DEV)
-    w = torch.randn(64, 3, 7, 7, device=DEV) / 147 ** 0.5
-    P, Q = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    Hp, Wp = max(H + 6, (P - 1) * 2 + 7), max(W + 6, (Q - 1) * 2 + 8)
-    xp = torch.empty(N * Hp * Wp * 4, device=DEV)
-    C.stem_pack32(x, xp, N, 3, H, W, 3, Hp, Wp)
-    ww = torch.zeros(64, 7, 8, 4, device=DEV)
-    ww[:, :, :7, :3] = w.permute(0, 2, 3, 1)
-    y = torch.empty(N * P * Q * 64, device=DEV)
-    st = torch.zeros(C.stat_slots() * 64 * 2, dtype=torch.float64, device=DEV)
-    C.conv32_stem_fwd(xp, ww.reshape(-1).contiguous(), y, st, N, Hp, Wp, 7, P, Q, 2, 64, *tile)
-    ref = F.conv2d(x, w, stride=2, padding=3).permute(0, 2, 3, 1)
-    assert _rel(y.view(N, P, Q, 64), ref) < 1e-5
-    s = st.view(-1, 64, 2).sum(0)
-    yf = y.view(-1, 64).double()
-    assert torch.allclose(s[:, 0], yf.sum(0), rtol=1e-5, atol=1e-3)
-    assert torch.allclose(s[:, 1], (yf * yf).sum(0), rtol=1e-5, atol=1e-3)
-
-
 def test_fp32_executor_window_stem_matches_im2col_stem(monkeypatch):
     """PDT_FP32_STEM_WIN=1 (window-mode stem forward) trains like the im2col stem: same loss / gradients to fp32
     rounding of a different summation order."""
@@ -318,34 +294,6 @@ def test_fp32_executor_window_stem_matches_im2col_stem(monkeypatch):
     assert _rel(outs[1][1], outs[0][1]) < 1e-4
     assert _rel(outs[1][3], outs[0][3]) < 5e-2, (outs[1][3][:8], outs[0][3][:8])
     assert _rel(outs[1][2], outs[0][2]) < 5e-2
-
-
-@pytest.mark.parametrize("all_pairs", [0, 1])
-def test_wgrad32_stem_window_pair_matches_torch(all_pairs):
-    """fp32 stem weight gradient in window-pair mode (tap = kernel-row pair over the padded NHWC4 image) vs
-    torch.nn.grad.conv2d_weight in fp32: one block per pair (wgrad32_kernel) and all 4 pairs per block
-    (wgrad32_stem4_kernel)."""
-    from pytorch_distributed_template_amd.ops import native
-    C = native.C
-    torch.manual_seed(4)
-    N, H, W = 3, 40, 36
-    x = torch.randn(N, 3, H, W, device=DEV)
-    P, Q = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    Hp, Wp = max(H + 6, (P - 1) * 2 + 8), max(W + 6, (Q - 1) * 2 + 8)
-    xp = torch.empty(N * Hp * Wp * 4, device=DEV)
-    C.stem_pack32(x, xp, N, 3, H, W, 3, Hp, Wp)
-    dy = torch.randn(N, P, Q, 64, device=DEV)
-    npix = N * P * Q
-    splits, pps = 7, ((npix + 6) // 7 + 63) // 64 * 64
-    splits = (npix + pps - 1) // pps
-    ws = torch.empty(splits * 64 * 256, device=DEV)
-    C.reset_dispatch_counts()
-    C.wgrad32_stem(xp, dy.contiguous(), ws, N, Hp, Wp, 4, 64, P, Q, 2, splits, pps, all_pairs)
-    assert dict(C.dispatch_counts()).get("wgrad32_stem4", 0) == all_pairs
-    dw = ws.view(splits, 64, 4, 2, 8, 4).sum(0)  # [k][pair][row in pair][pixel s][channel]
-    dw = dw.reshape(64, 8, 8, 4)[:, :7, :7, :3].permute(0, 3, 1, 2)  # rows 0..7 -> 7 kernel rows
-    ref = torch.nn.grad.conv2d_weight(x, (64, 3, 7, 7), dy.permute(0, 3, 1, 2), stride=2, padding=3)
-    assert _rel(dw, ref) < 1e-5
 
 
 def test_fp32_fused_bn_backward_reduce_matches_separate_pass(monkeypatch):
@@ -447,44 +395,6 @@ def test_fp32_fused_stem_tail_matches_the_separate_passes(monkeypatch):
         assert (cnt.get("stem_pool_bwd_fused32", 0) + cnt.get("stem_pool_bwd_reduce_out32", 0) > 0) == fuse
         outs.append(tr.flat.grad.clone())
     assert _rel(outs[1], outs[0]) < 1e-5
-
-
-def test_wgrad32_stem_fused_dy_matches_apply_then_wgrad():
-    """The 4-pair fp32 stem weight gradient with dY computed in the kernel (max-pool backward from the pooled gradient
-    and argmax, ReLU mask, BN-backward apply) equals stem_pool_bwd_apply32 followed by the plain 4-pair kernel: same
-    float operations in the same order -- random argmax codes included (border windows whose code points outside the
-    image select nothing in both), an odd pooled width, and a split whose last chunk is partial."""
-    from pytorch_distributed_template_amd.ops import native
-    C = native.C
-    torch.manual_seed(6)
-    N, H, W = 2, 42, 38
-    x = torch.randn(N, 3, H, W, device=DEV)
-    P, Q = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    OH, OW = (P - 1) // 2 + 1, (Q - 1) // 2 + 1
-    Hp, Wp = max(H + 6, (P - 1) * 2 + 8), max(W + 6, (Q - 1) * 2 + 8)
-    xp = torch.empty(N * Hp * Wp * 4, device=DEV)
-    C.stem_pack32(x, xp, N, 3, H, W, 3, Hp, Wp)
-    y0 = torch.randn(N * P * Q * 64, device=DEV)
-    dp = torch.randn(N * OH * OW * 64, device=DEV)
-    idx = torch.randint(0, 9, (N * OH * OW * 64,), device=DEV, dtype=torch.uint8)
-    coef = torch.cat([torch.rand(64, device=DEV) + 0.5, torch.randn(64, device=DEV) * 0.3,  # scale | shift
-                      torch.randn(64, device=DEV), torch.rand(64, device=DEV) + 0.5])  # mean | invstd
-    bcoef = torch.randn(192, device=DEV)
-    npix = N * P * Q
-    pps = ((npix + 4) // 5 + 63) // 64 * 64
-    splits = (npix + pps - 1) // pps
-    assert npix % 32 != 0 or splits * pps > npix
-    dy = torch.empty(npix * 64, device=DEV)
-    C.stem_pool_bwd_apply32(dp, idx, y0, coef, bcoef, dy, N, P, Q, 64)
-    ws_ref = torch.zeros(splits * 64 * 256, device=DEV)
-    C.wgrad32_stem(xp, dy, ws_ref, N, Hp, Wp, 4, 64, P, Q, 2, splits, pps, 1)
-    ws = torch.zeros(splits * 64 * 256, device=DEV)
-    C.reset_dispatch_counts()
-    C.wgrad32_stem_fused(xp, dp, idx, y0, coef, bcoef, ws, N, Hp, Wp, P, Q, 2, splits, pps)
-    torch.cuda.synchronize()
-    assert dict(C.dispatch_counts()).get("wgrad32_stem4_fused", 0) == 1
-    assert _rel(ws, ws_ref) < 1e-6, _rel(ws, ws_ref)
-    print("bit-identical:", torch.equal(ws, ws_ref))
 
 
 def test_stem_pool_bwd_reduce_out32_matches_window_gather():

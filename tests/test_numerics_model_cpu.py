@@ -623,3 +623,311 @@ def test_element_assertion_rejects_a_value_from_another_group_slice(layer, dtype
         bad = good.clone()
         bad[n, p, q, k] = good[n, p, q, k + 64]
         _expect_reject(layer, bad, ref, mag, 64 * 9, dtype)
+
+
+# =================================================================================== the fp32 conv error model (fp32 MFMA)
+# The same proofs for dtype float32 (tests/test_conv32_numerics_gpu.py): the integer cases are exact, two correct fp32
+# evaluations stay inside the real bound, the assertions reject the mutations, and the ``wide`` layer holds the width of
+# the multiply.
+F32 = torch.float32
+_nchw = lambda t: t.float().permute(0, 3, 1, 2)  # noqa: E731
+
+
+def _rec32(family, worst):
+    nm.RATIOS[family] = max(nm.RATIOS.get(family, 0.0), worst)
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("kind,g,opt", cc.layer_a_cases32(), ids=lambda v: str(v).replace(" ", ""))
+def test_layer_a32_cases_are_exact_and_plain_fp32_equals_fp64(kind, g, opt):
+    """max |mag| < 2**24 (every partial sum is an exact integer), every per-channel sum of squares of the outputs below
+    2**24 (the statistics are exact), and a plain torch fp32 evaluation equals the fp64 reference."""
+    N, H, W, C, K, R, st, pad = g
+    if kind == "fwd":
+        x, w, res = cc.fwd_operands(g, F32, "int", residual=True)
+        ref, mag = nm.conv_fwd_ref(x, w, st, pad, res)
+        plain = F.conv2d(_nchw(x), _nchw(w), stride=st, padding=pad).permute(0, 2, 3, 1) + res
+        ch = K
+    elif kind == "dgrad":
+        dy, w, res = cc.dgrad_operands(g, F32, "int", "full")
+        ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+        plain = torch.nn.grad.conv2d_input((N, C, H, W), _nchw(w), _nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1) \
+            + res
+        ch = C
+    elif kind == "wgrad":
+        x, dy = cc.wgrad_operands(g, F32, "int")
+        ref, mag = nm.conv_wgrad_ref(x, dy, R, R, st, pad)
+        plain = torch.nn.grad.conv2d_weight(_nchw(x), (K, C, R, R), _nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1)
+        ch = None
+    else:
+        x, w, dy = cc.stem32_operands(N, H, W, "int")
+        ref, mag = nm.conv_fwd_ref(x.permute(0, 2, 3, 1), w, 2, 3)
+        plain = F.conv2d(x, _nchw(w), stride=2, padding=3).permute(0, 2, 3, 1)
+        ch = 64
+        wref, wmag = nm.conv_wgrad_ref(x.permute(0, 2, 3, 1), dy, 7, 7, 2, 3)
+        assert float(wmag.max()) < 2.0 ** 24
+    assert float(mag.max()) < 2.0 ** 24
+    if ch is not None:
+        top, sumsq = nm.int32_case_conditions(ref, mag, ch)
+        assert sumsq < 2.0 ** 24, sumsq
+    assert bool((ref == ref.round()).all()) and bool((ref != 0).any())
+    assert torch.equal(plain.double(), ref)
+
+
+@pytest.mark.parametrize("g", [cc.C32_TILE_GEOM, cc.C32_TILE_GEOM_256] + [cc.dgrad_geom32(g) for g in cc.C32_HALO_GEOMS],
+                         ids=str)
+def test_layer_a32_fused_bn_backward_sums_are_exact_and_few_signs_are_uncertain(g):
+    """The exact BN operands give sums in quarters below 2**22 (exact in fp32) with no uncertain sign; the real operands
+    of the bn_mref = None epilogue leave out far less than 1 % of the elements."""
+    N, H, W, C, K, R, st, pad = g
+    for mode, res in ((1, None), (2, "full"), (3, "full")):
+        dy, w, r = cc.dgrad_operands(g, F32, "int", res)
+        ref, _ = nm.conv_dgrad_ref(dy, w, H, W, st, pad, r)
+        d = cc.bnb_operands(mode, (N, H, W, C), F32, "int")
+        mask, unsure = cc.bnb_mask(mode, d, C)
+        assert not bool(unsure.any())
+        dz = torch.where(mask, ref.reshape(-1, C), torch.zeros((), dtype=torch.float64))
+        for k in (1, 2) if mode == 3 else (1,):
+            xh = nm.bn_xhat(d[f"y{k}"], d[f"coef{k}"], C)
+            assert float((dz * xh).abs().sum(0).max()) < 2.0 ** 22
+            assert bool(((dz * xh * 4) == (dz * xh * 4).round()).all())
+    _, unsure = cc.bnb_mask(1, cc.bnb_operands(1, (N, H, W, C), F32, "real"), C)
+    assert float(unsure.double().mean()) < 0.01
+
+
+EMUL32_GEOMS = cc.C32_DEFAULT_GEOMS[:5] + [cc.C32_HALO_GEOMS[3]]
+
+
+@pytest.mark.parametrize("g", EMUL32_GEOMS, ids=str)
+def test_fp32_emulations_of_the_fp32_convs_stay_within_the_bounds(g):
+    """Plain torch fp32 and the adversarially grouped fp32 evaluation on the real operands: inside (n + 5)*2u*mag;
+    ratios recorded as cpu_plain_conv32_* / cpu_grouped_conv32_*."""
+    N, H, W, C, K, R, st, pad = g
+    P, Q = cc.out_hw(g)
+    x, w, res = cc.fwd_operands(g, F32, "real", residual=True)
+    ref, mag = nm.conv_fwd_ref(x, w, st, pad, res)
+    assert float(ref[..., 1].abs().max()) < 0.05  # the small channel
+    plain = F.conv2d(_nchw(x), _nchw(w), stride=st, padding=pad).permute(0, 2, 3, 1) + res
+    _rec32("cpu_plain_conv32_fwd", nm.assert_conv32(plain, ref, mag, C * R * R, "plain fwd", None))
+    cols = F.unfold(_nchw(x), (R, R), padding=pad, stride=st)
+    grp = _grouped_sum(_nchw(w).reshape(K, C * R * R), cols, C * R * R).view(N, K, P, Q).permute(0, 2, 3, 1) + res
+    _rec32("cpu_grouped_conv32_fwd", nm.assert_conv32(grp, ref, mag, C * R * R, "grouped fwd", None))
+    yf = plain.reshape(-1, K)
+    s, ss = torch.zeros(K), torch.zeros(K)
+    for r in range(yf.shape[0]):
+        s, ss = s + yf[r], ss + yf[r] * yf[r]
+    _rec32("cpu_plain_conv32_stats", nm.assert_conv_stats(s, ss, plain, "stats chain", family=None))
+    gd = g if C % 64 == 0 else cc.dgrad_geom32(g)
+    N, H, W, C, K, R, st, pad = gd
+    dy, w, res = cc.dgrad_operands(gd, F32, "real", "full")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+    plain = torch.nn.grad.conv2d_input((N, C, H, W), _nchw(w), _nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1) + res
+    _rec32("cpu_plain_conv32_dgrad", nm.assert_conv32(plain, ref, mag, K * R * R, "plain dgrad", None))
+    dil, wt = nm.dgrad_as_correlation(dy, w, H, W, st, pad, torch.float32)
+    grp = _grouped_sum(wt, F.unfold(dil, (R, R)), K * R * R).view(N, C, H, W).permute(0, 2, 3, 1) + res
+    _rec32("cpu_grouped_conv32_dgrad", nm.assert_conv32(grp, ref, mag, K * R * R, "grouped dgrad", None))
+    N, H, W, C, K, R, st, pad = g
+    x, dy = cc.wgrad_operands(g, F32, "real")
+    ref, mag = nm.conv_wgrad_ref(x, dy, R, R, st, pad)
+    plain = torch.nn.grad.conv2d_weight(_nchw(x), (K, C, R, R), _nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1)
+    _rec32("cpu_plain_conv32_wgrad", nm.assert_conv32(plain, ref, mag, N * P * Q, "plain wgrad", None))
+    cols = F.unfold(_nchw(x), (R, R), padding=pad, stride=st).permute(1, 0, 2).reshape(C * R * R, N * P * Q)
+    grp = _grouped_sum(cols, dy.reshape(N * P * Q, K), N * P * Q).view(C, R, R, K).permute(3, 1, 2, 0)
+    _rec32("cpu_grouped_conv32_wgrad", nm.assert_conv32(grp, ref, mag, N * P * Q, "grouped wgrad", None))
+
+
+@pytest.mark.parametrize("mode", [1, 2, 3])
+def test_fp32_emulation_of_the_fp32_fused_bn_backward_sums_stays_within_the_bound(mode):
+    g = (2, 14, 9, 64, 64, 3, 1, 1)
+    N, H, W, C, K, R, st, pad = g
+    dy, w, res = cc.dgrad_operands(g, F32, "real", None if mode == 1 else "full")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+    d = cc.bnb_operands(mode, (N, H, W, C), F32, "real")
+    mask, unsure = cc.bnb_mask(mode, d, C)
+    plain = torch.nn.grad.conv2d_input((N, C, H, W), _nchw(w), _nchw(dy), stride=st, padding=pad).permute(0, 2, 3, 1)
+    if res is not None:
+        plain = plain + res
+    m32 = (d["y1"].view(-1, C) * d["coef1"][:C] + d["coef1"][C:2 * C]) > 0 if mode == 1 else mask
+    dz = torch.where(m32, plain.reshape(-1, C), torch.zeros(()))
+    ref2 = torch.where(mask, ref.reshape(-1, C), torch.zeros((), dtype=torch.float64))
+    full = nm.conv32_bound(mag, K * R * R).reshape(-1, C)
+    sb = torch.where(unsure, ref.reshape(-1, C).abs() + full, torch.where(mask, full, torch.zeros_like(full)))
+    for k in (1, 2) if mode == 3 else (1,):
+        yk, ck = d[f"y{k}"], d[f"coef{k}"]
+        xh32 = (yk.view(-1, C) - ck[2 * C:3 * C]) * ck[3 * C:]
+        s0, s1 = torch.zeros(C), torch.zeros(C)
+        for r in range(dz.shape[0]):
+            s0, s1 = s0 + dz[r], s1 + dz[r] * xh32[r]
+        _rec32("cpu_plain_conv32_bnb_sums",
+               nm.assert_bnb_sums(s0, s1, ref2, sb, nm.bn_xhat(yk, ck, C), f"branch {k}", family=None))
+
+
+def _stem_fused_cpu(N, H, W, layer):
+    P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    x, _, _ = cc.stem32_operands(N, H, W, layer)
+    d = cc.stem32_tail_operands(N, P, Q, layer)
+    r = cc.stem_tail_ref(d, N, P, Q, 64)
+    xh = x.permute(0, 2, 3, 1)
+    ref, _ = nm.conv_wgrad_ref(xh, r["dy"], 7, 7, 2, 3)
+    _, mag = nm.conv_wgrad_ref(xh, r["dymag"], 7, 7, 2, 3)
+    _, flip = nm.conv_wgrad_ref(xh, r["dyflip"], 7, 7, 2, 3)
+    return x, d, r, ref, mag, flip
+
+
+@pytest.mark.parametrize("N,H,W", cc.STEM32_FUSED[:1] + cc.STEM32_FUSED[2:3])
+def test_fp32_emulation_of_the_fused_stem_weight_gradient(N, H, W):
+    """dY formed in fp32 (scatter, mask, A*dz + B*y + C) and torch's fp32 conv2d_weight: inside (n + 12)*2u*mag on the
+    real operands and equal to the fp64 reference on the exact ones; a dY built from argmax codes shifted by one is
+    rejected by both layers."""
+    P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    for layer in ("int", "real"):
+        x, d, r, ref, mag, flip = _stem_fused_cpu(N, H, W, layer)
+
+        def emul(idx):
+            r32 = cc.stem_tail_ref(dict(d, idx=idx), N, P, Q, 64)
+            pre = d["y"] * d["coef"][:64] + d["coef"][64:128]
+            dz = torch.where(pre > 0, r32["dzraw"].float(), torch.zeros(()))  # the fp32 mask on the rounded scatter
+            dy = d["b"][:64] * dz + d["b"][64:128] * d["y"] + d["b"][128:192]
+            return torch.nn.grad.conv2d_weight(x, (64, 3, 7, 7), _nchw(dy), stride=2, padding=3).permute(0, 2, 3, 1)
+        bound = nm.conv32_bound(mag, N * P * Q, extra=12) + flip
+        good, bad = emul(d["idx"]), emul((d["idx"] + 1) % 9)
+        if layer == "int":
+            assert not bool(r["unsure"].any()) and float(mag.max()) < 2.0 ** 23
+            nm.assert_exact(good, ref, "stem fused emulation")
+            with pytest.raises(AssertionError, match="out of bound"):
+                nm.assert_exact(bad, ref, "shifted argmax")
+        else:
+            _rec32("cpu_plain_conv32_stem_fused", nm.assert_within(good, ref, bound, "stem fused emulation", 3, None))
+            with pytest.raises(AssertionError, match="out of bound"):
+                nm.assert_within(bad, ref, bound, "shifted argmax", 3, None)
+
+
+def _check32(layer, out, ref, mag, n):
+    if layer == "int":
+        nm.assert_exact(out, ref, "case")
+    else:
+        nm.assert_conv32(out, ref, mag, n, "case", None)
+
+
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_fp32_element_assertions_reject_a_dropped_tap_a_neighbouring_channel_and_residual_mistakes(layer):
+    g = (2, 14, 9, 64, 64, 3, 1, 1)
+    N, H, W, C, K, R, st, pad = g
+    x, w, res = cc.fwd_operands(g, F32, layer, residual=True)
+    ref, mag = nm.conv_fwd_ref(x, w, st, pad, res)
+    conv = F.conv2d(_nchw(x), _nchw(w), padding=pad).permute(0, 2, 3, 1)
+    good = conv + res
+    _check32(layer, good, ref, mag, C * 9)
+    for (n, p, q, k) in _positions(ref, N, H, W) + [(1, 3, 4, 1)]:  # ... and the small channel
+        t, xin = _terms(x, w, n, p, q, k, st, pad)
+        r0 = float(res[n, p, q, k])
+        assert abs(float(t.sum()) + r0 - float(ref[n, p, q, k])) < 1e-9
+        drop_tap = t.clone()
+        drop_tap[:, 1, 1] = 0
+        c1 = next(c for c in range(5, C - 1) if float((xin[c + 1] * w[k, :, :, c].double() - t[c]).sum()) != 0)
+        neigh = t.clone()
+        neigh[c1] = xin[c1 + 1] * w[k, :, :, c1].double()
+        q2 = q + 1 if q + 1 < W else q - 1
+        for val in (float(drop_tap.sum()) + r0, float(neigh.sum()) + r0, float(t.sum()) + 2 * r0,
+                    float(t.sum()) + float(res[n, p, q2, k])):  # dropped tap, neighbour, doubled / misplaced residual
+            if val == float(ref[n, p, q, k]):
+                continue  # (integer terms can cancel)
+            bad = good.clone()
+            bad[n, p, q, k] = val
+            with pytest.raises(AssertionError, match="out of bound"):
+                _check32(layer, bad, ref, mag, C * 9)
+    # a transposed H / W in the reference is seen by a correct result (the inverted reference check)
+    xt = x.transpose(1, 2).contiguous().view(N, H, W, C) if H != W else x
+    rt, _ = nm.conv_fwd_ref(xt, w, st, pad, res)
+    with pytest.raises(AssertionError, match="index"):
+        _check32(layer, good, rt, mag, C * 9)
+
+
+@pytest.mark.parametrize("layer", ["int", "real"])
+def test_fp32_statistics_and_bn_backward_sum_assertions_reject_a_missing_row_and_swapped_branches(layer):
+    g = (2, 14, 9, 64, 64, 3, 1, 1)
+    N, H, W, C, K, R, st, pad = g
+    exact = layer == "int"
+    x, w, _ = cc.fwd_operands(g, F32, layer)
+    y = F.conv2d(_nchw(x), _nchw(w), padding=1).permute(0, 2, 3, 1)
+    y64 = y.double().reshape(-1, K)
+    s, ss = y64.sum(0), (y64 * y64).sum(0)
+    nm.assert_conv_stats(s, ss, y, "correct", family=None, exact=exact)
+    for row in (y64.shape[0] - 2, 0):
+        with pytest.raises(AssertionError, match="out of bound"):
+            nm.assert_conv_stats(s - y64[row], ss, y, "sum", family=None, exact=exact)
+        with pytest.raises(AssertionError, match="out of bound"):
+            nm.assert_conv_stats(s, ss - y64[row] ** 2, y, "sumsq", family=None, exact=exact)
+    dy, w, res = cc.dgrad_operands(g, F32, layer, "full")
+    ref, mag = nm.conv_dgrad_ref(dy, w, H, W, st, pad, res)
+    d = cc.bnb_operands(3, (N, H, W, C), F32, layer)
+    mask, _ = cc.bnb_mask(3, d, C)
+    dz = torch.where(mask, ref.reshape(-1, C), torch.zeros((), dtype=torch.float64))
+    full = nm.conv32_bound(mag, K * 9).reshape(-1, C)
+    bound = torch.where(mask, full, torch.zeros_like(full))
+    x1, x2 = nm.bn_xhat(d["y1"], d["coef1"], C), nm.bn_xhat(d["y2"], d["coef2"], C)
+    nm.assert_bnb_sums(dz.sum(0), (dz * x2).sum(0), dz, bound, x2, "correct", family=None, exact=exact)
+    with pytest.raises(AssertionError, match="out of bound"):
+        nm.assert_bnb_sums(dz.sum(0), (dz * x1).sum(0), dz, bound, x2, "branch 2", family=None, exact=exact)
+    c12 = torch.cat([d["coef2"][:2 * C], d["coef1"][2 * C:]])
+    with pytest.raises(AssertionError, match="out of bound"):
+        nm.assert_bnb_sums(dz.sum(0), (dz * nm.bn_xhat(d["y2"], c12, C)).sum(0), dz, bound, x2, "branch 2", family=None,
+                           exact=exact)
+    with pytest.raises(AssertionError, match="out of bound"):  # one row missing from the fused sums
+        nm.assert_bnb_sums((dz.sum(0) - dz[-2]), ((dz * x1).sum(0) - (dz * x1)[-2]), dz, bound, x1, "branch 1",
+                           family=None, exact=exact)
+
+
+@pytest.mark.parametrize("variant", cc.WIDE_VARIANTS)
+def test_wide_layer_accepts_plain_fp32_and_rejects_19_bit_products_and_operands(variant):
+    """Plain fp32 is exact on every ``wide`` case; a product rounded to 19 bits mismatches EVERY element of (a); an
+    operand rounded to 19 bits on the 24-bit side mismatches every element of (b) and (c)."""
+    g = cc.WIDE_FWD[1]
+    N, H, W, C, K, R, st, pad = g
+    x, w = cc.wide_fwd_operands(g, variant)
+    ref, _ = nm.conv_fwd_ref(x, w, 1, 0)
+    assert bool((ref != 0).all()) and bool((x != 0).sum(-1).eq(1).all())
+    y = F.conv2d(_nchw(x), _nchw(w)).permute(0, 2, 3, 1)
+    nm.assert_exact(y, ref, "plain fp32")
+    if variant == "a":
+        narrow = nm.round_to_bits(y, 19)
+        assert bool((narrow.double() != ref).all())
+    else:
+        xs, ws = (nm.round_to_bits(x, 19), w) if variant == "b" else (x, nm.round_to_bits(w, 19))
+        narrow = F.conv2d(_nchw(xs), _nchw(ws)).permute(0, 2, 3, 1)
+        assert bool((narrow.double() != ref).all())
+    with pytest.raises(AssertionError, match="out of bound"):
+        nm.assert_exact(narrow, ref, "19 bits")
+    gd = cc.dgrad_geom32(g)
+    dy, wd = cc.wide_dgrad_operands(gd, variant)
+    refd, _ = nm.conv_dgrad_ref(dy, wd, H, W, 1, 0)
+    dx = torch.nn.grad.conv2d_input((N, K, H, W), _nchw(wd), _nchw(dy)).permute(0, 2, 3, 1)
+    assert bool((refd != 0).all())
+    nm.assert_exact(dx, refd, "plain fp32 dgrad")
+    for gw, tile in cc.WIDE_WGRAD:
+        xw, dyw = cc.wide_wgrad_operands(gw, variant)
+        refw, _ = nm.conv_wgrad_ref(xw, dyw, 1, 1, 1, 0)
+        assert bool((refw != 0).all())
+        dw = torch.einsum("pc,pk->kc", xw.reshape(-1, gw[3]), dyw.reshape(-1, gw[4])).view(gw[4], 1, 1, gw[3])
+        nm.assert_exact(dw, refw, "plain fp32 wgrad")
+        with pytest.raises(AssertionError, match="out of bound"):
+            nm.assert_exact(nm.round_to_bits(dw, 19) if variant == "a" else torch.einsum(
+                "pc,pk->kc", nm.round_to_bits(xw, 19).reshape(-1, gw[3]),
+                nm.round_to_bits(dyw, 19).reshape(-1, gw[4])).view(gw[4], 1, 1, gw[3]), refw, "19 bits")
+
+
+def test_real_bound_at_32_terms_rejects_11_bit_operands_and_long_reductions_do_not():
+    """The real layer owns scaling and rounding-mode errors, not the width of the multiply: at n = 32 operands rounded
+    to 11 bits fail the bound, at n = 4608 even 8-bit operands pass it (hence the ``wide`` layer)."""
+    g = cc.WIDE_FWD[0]
+    x, w, _ = cc.fwd_operands(g, F32, "real")
+    ref, mag = nm.conv_fwd_ref(x, w, 1, 0)
+    nm.assert_conv32(F.conv2d(_nchw(x), _nchw(w)).permute(0, 2, 3, 1), ref, mag, 32, "plain", None)
+    r11, _ = nm.conv_fwd_ref(nm.round_to_bits(x, 11), nm.round_to_bits(w, 11), 1, 0)
+    with pytest.raises(AssertionError, match="out of bound"):
+        nm.assert_conv32(r11, ref, mag, 32, "11-bit operands", None)
+    g = (2, 8, 6, 512, 128, 3, 1, 1)
+    x, w, _ = cc.fwd_operands(g, F32, "real")
+    ref, mag = nm.conv_fwd_ref(x, w, 1, 1)
+    r8, _ = nm.conv_fwd_ref(nm.round_to_bits(x, 8), nm.round_to_bits(w, 8), 1, 1)
+    nm.assert_conv32(r8, ref, mag, 4608, "8-bit operands at n = 4608", None)
