@@ -208,11 +208,14 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_reduce_kernel(const uint16_
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int pos0 = (int)((((e < 4) ? ib.x : ib.y) >> (8 * (e & 3))) & 0xff);
-        // a dead window (255: its maximum is the ReLU's zero) passes nothing; it reads the always-inside centre tap
-        const bool live = pos0 < 9;
-        const int pos = live ? pos0 : 4;
+        // a dead window (255: its maximum is the ReLU's zero) passes nothing, and neither does a code that points
+        // outside the image (bn_relu_maxpool writes none; the gather-form kernels ignore them too): both read the
+        // always-inside centre tap, never memory outside y
+        const int pos = pos0 < 9 ? pos0 : 4;
         const int kh = pos / 3, kw = pos - 3 * (pos / 3);
-        const int h = oh * 2 - 1 + kh, w = ow * 2 - 1 + kw;  // always inside (argmax is a valid tap)
+        const int th = oh * 2 - 1 + kh, tw = ow * 2 - 1 + kw;
+        const bool live = pos0 < 9 && (unsigned)th < (unsigned)H && (unsigned)tw < (unsigned)W;
+        const int h = live ? th : oh * 2, w = live ? tw : ow * 2;
         const float yv = E::to_f(ybase[((int64_t)h * W + w) * C + e]);
         const float dz = (live && yv * sc[e] + sh[e] > 0.f) ? E::to_f(gh[e]) : 0.f;
         s[0][e] += dz;

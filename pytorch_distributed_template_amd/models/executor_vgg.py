@@ -103,6 +103,31 @@ def vgg_supported(model) -> bool:
     return True
 
 
+def first_conv_maps(cout: int, R: int, src_offset: int = 0):
+    """Index maps of the 3-channel first conv (R x R, KRSC weight [cout][R][R][3] at ``src_offset`` of the flat 16-bit
+    parameters) in window mode: returns (win, gidx, T, U, ldw), both maps int32 on the CPU.
+
+    ``win`` gathers (``gather16``; -1: zero) the forward window weights [cout][R][U][32]: window u of kernel row r holds
+    columns u*8 .. u*8+7, element j = column (j // 4) * 4 + channel (j % 4) of the NHWC4 image (U = 1 for VGG's 3x3, 2
+    for AlexNet's 11x11).  ``gidx`` gathers (``gather32``) the KRSC gradient [cout][R][R][3] out of the weight
+    gradient's window tile [cout][T kernel-row pairs][U windows][2 rows][32] of row stride ``ldw`` = T * U * 64; the
+    second row of the last pair of an odd R and the columns past R are padding and are dropped."""
+    U0 = (R + 7) // 8
+    T0 = (R + 1) // 2  # weight-gradient kernel-row pairs
+    k = torch.arange(cout).view(-1, 1, 1, 1)
+    r = torch.arange(R).view(1, -1, 1, 1)
+    u = torch.arange(U0).view(1, 1, -1, 1)
+    j = torch.arange(32).view(1, 1, 1, -1)
+    s_, c_ = u * 8 + j // 4, j % 4
+    src = src_offset + ((k * R + r) * R + s_.clamp(max=R - 1)) * 3 + c_.clamp(max=2)
+    win = torch.where((s_ < R) & (c_ < 3), src, torch.full_like(src, -1))
+    ldw = T0 * U0 * 64
+    ss = torch.arange(R).view(1, 1, -1, 1)
+    cc = torch.arange(3).view(1, 1, 1, -1)
+    gidx = (k * ldw + ((r // 2) * U0 + ss // 8) * 64 + (r % 2) * 32 + (ss % 8) * 4 + cc).reshape(-1).to(torch.int32)
+    return win.reshape(-1).to(torch.int32), gidx, T0, U0, ldw
+
+
 class VGGExecutor(ResNetExecutor):
     """Runs a torchvision-layout :class:`VGG` or :class:`AlexNet` on one GPU (same public interface as
     :class:`ResNetExecutor`)."""
@@ -178,32 +203,14 @@ class VGGExecutor(ResNetExecutor):
                 pool = _pool_kind(mods[i])
                 i += 1
             self.layers.append(_Layer(conv, bn, pool, flat, derived_maps, off, self.device))
-        # the first conv's window weights [cout][R][U][32]: window u of kernel row r holds columns u*8 .. u*8+7,
-        # element j = column (j // 4) * 4 + channel (j % 4) of the NHWC4 image (U = 1 for VGG's 3x3, 2 for the 11x11)
         first = self.layers[0]
         assert first.first and all(not l.first for l in self.layers[1:]), "3-channel input conv first"
         fc = first.conv
-        R0 = fc.R
-        self.w0_U = U0 = (R0 + 7) // 8
-        self.w0_T = T0 = (R0 + 1) // 2  # weight-gradient kernel-row pairs
-        k = torch.arange(fc.cout).view(-1, 1, 1, 1)
-        r = torch.arange(R0).view(1, -1, 1, 1)
-        u = torch.arange(U0).view(1, 1, -1, 1)
-        j = torch.arange(32).view(1, 1, 1, -1)
-        s_, c_ = u * 8 + j // 4, j % 4
-        src = fc.slot.offset + ((k * R0 + r) * R0 + s_.clamp(max=R0 - 1)) * 3 + c_.clamp(max=2)
-        win = torch.where((s_ < R0) & (c_ < 3), src, torch.full_like(src, -1))
+        win, gidx, self.w0_T, self.w0_U, self.w0_ldw = first_conv_maps(fc.cout, fc.R, fc.slot.offset)
         self.w0_off = off[0]
-        derived_maps.append(win.reshape(-1).to(torch.int32))
+        derived_maps.append(win)
         off[0] += win.numel()
-        # its weight gradient: [cout][T pairs][U windows][2 rows][32] window tile -> KRSC [cout][R][R][3]
-        self.w0_ldw = T0 * U0 * 64
-        kk = torch.arange(fc.cout).view(-1, 1, 1, 1)
-        rr = torch.arange(R0).view(1, -1, 1, 1)
-        ss = torch.arange(R0).view(1, 1, -1, 1)
-        cc = torch.arange(3).view(1, 1, 1, -1)
-        self.w0_gidx = (kk * self.w0_ldw + ((rr // 2) * U0 + ss // 8) * 64 + (rr % 2) * 32 + (ss % 8) * 4 +
-                        cc).reshape(-1).to(torch.int32).to(self.device)
+        self.w0_gidx = gidx.to(self.device)
         # --- classifier: VGG [Linear, ReLU, Dropout] x 2 + Linear; AlexNet [Dropout, Linear, ReLU] x 2 + Linear
         lin = [m for m in model.classifier if isinstance(m, nn.Linear)]
         drops = [m for m in model.classifier if isinstance(m, nn.Dropout)]

@@ -31,7 +31,13 @@ DEFAULT_GEOMS = [
     (2, 12, 12, 64, 256, 1, 1, 0),   # one K-step
     (1, 9, 9, 128, 128, 3, 1, 1),
     (2, 8, 8, 512, 512, 3, 1, 1),
+    (2, 13, 13, 64, 192, 5, 1, 2),   # AlexNet's 5x5 conv (at 64 input channels)
+    (2, 7, 7, 192, 384, 3, 1, 1),    # AlexNet's third conv
 ]
+# AlexNet's shapes on the weight-gradient kernels (the planner's own tile), and its classifier: a 1x1 conv over
+# H = W = 1, a few pixels per split, whose wgrad_reduce crops the rows to cout - 28 (the padded last Linear)
+WGRAD_ALEXNET = [(2, 13, 13, 64, 192, 5, 1, 2), (2, 7, 7, 192, 384, 3, 1, 1)]
+WGRAD_CLASSIFIER = [(5, 1, 1, 128, 128, 1, 1, 0), (130, 1, 1, 192, 256, 1, 1, 0)]
 PP_GEOMS = [
     (5, 14, 14, 256, 256, 3, 1, 1),  # 4 tiles of 256 rows, ragged tail, 36 K-steps
     (5, 14, 14, 192, 256, 3, 1, 1),  # 27 K-steps (odd)
@@ -54,6 +60,9 @@ WGRAD_WIDE = [(3, 6, 6, 128, 128, 3, 2, 1), (1, 7, 7, 384, 128, 3, 1, 1)]
 WGRAD_PP = [(6, 14, 14, 256, 256, 3, 1, 1)]
 WGRAD_L1 = (5, 22, 56)  # conv_wgrad_3x3c64: N, H, W (H % 4 != 0: a partial last row tile)
 WGRAD_TARGETS = [64, 2048]
+# the 3-channel first conv on the generic window kernels (R, stride, pad, N, H, W): AlexNet's 11x11/4 (two 8-pixel windows
+# per kernel row), VGG's 3x3/1, a 5x5/2, and a 9x9/3 (two windows, an odd R: a padding kernel row in the last pair)
+FIRST_CONV = [(11, 4, 2, 2, 39, 35), (3, 1, 1, 2, 10, 12), (5, 2, 2, 2, 13, 11), (9, 3, 4, 2, 20, 23)]
 STEM = [(3, 32, 32), (65, 32, 32)]  # N, H, W of the image; 65 images: 260 four-row tiles, more than 256 blocks
 
 
@@ -217,6 +226,27 @@ def stem_operands(N, H, W, dtype, layer):
     return torch.randn(N, 3, H, W, generator=gen), (torch.randn(64, 7, 7, 3, generator=gen) * 0.05).to(dtype)
 
 
+def first_conv_geom(case):
+    R, st, pad, N, H, W = case
+    return (N, H, W, 3, 64, R, st, pad)
+
+
+def first_conv_operands(case, dtype, layer):
+    """(fp32 NCHW image, KRSC weight [64, R, R, 3] in ``dtype``, dY [N, P, Q, 64] in ``dtype``) of a ``FIRST_CONV``
+    case."""
+    R, st, pad, N, H, W = case
+    P, Q = out_hw(first_conv_geom(case))
+    sd = 300 + 17 * R + H
+    if layer == "int":
+        return (nm.conv_int_operands((N, 3, H, W), XVALS, sd), nm.conv_int_operands((64, R, R, 3), WVALS, sd + 1).to(dtype),
+                nm.conv_int_operands((N, P, Q, 64), XVALS, sd + 2).to(dtype))
+    gen = torch.Generator().manual_seed(sd)
+    w = torch.randn(64, R, R, 3, generator=gen) * (1.0 / (3 * R * R)) ** 0.5
+    if dtype in SMALL_CHANNEL:
+        w[1] *= 1e-3
+    return torch.randn(N, 3, H, W, generator=gen), w.to(dtype), torch.randn(N, P, Q, 64, generator=gen).to(dtype)
+
+
 def pre_apply_ref(z, coef, dtype):
     """relu(z * scale + shift) as the fused kernels form it: one fp32 fma, rounded to the 16-bit type."""
     z64 = z.to(torch.float64)
@@ -245,7 +275,7 @@ def grouped_weights(width, groups, dtype, layer, seed=3):
 # ---- every layer-A case: (name, kind, geometry, options) -- test_numerics_model_cpu checks the representability cap
 # and the sum-of-squares condition on each of them; test_conv_numerics_gpu runs them.  ``narrow``: activations from
 # {-1, 1} (the wider set breaks the 1 % cap at this reduction length).
-NARROW = {(2, 8, 8, 512, 512, 3, 1, 1)}
+NARROW = {(2, 8, 8, 512, 512, 3, 1, 1), (2, 13, 13, 64, 192, 5, 1, 2)}  # the second: its data gradient, 4800 terms
 
 
 def layer_a_cases():
@@ -268,6 +298,8 @@ def layer_a_cases():
         out.append(("grouped_dgrad", grouped_geom(width, groups, stride, H), {"groups": groups}))
     for N, H, W in STEM:
         out.append(("stem", (N, H, W, 3, 64, 7, 2, 3), {}))
+    for case in FIRST_CONV:
+        out.append(("first", first_conv_geom(case), {}))
     seen, uniq = set(), []
     for kind, g, opt in out:
         key = (kind, g, tuple(sorted(opt.items())))
@@ -450,20 +482,74 @@ def stem32_tail_operands(N, P, Q, layer, C=64, seed=0):
     return dict(y=y, dp=dp, idx=idx, coef=coef.contiguous(), b=b.contiguous())
 
 
-def stem_tail_ref(d, N, P, Q, C):
-    """Independent fp64 reference of the stem's backward tail from ``stem32_tail_operands`` (any device): the pooled
-    gradient scattered along the argmax bytes (codes pointing outside the image select nothing), the ReLU mask from
+def pool_out_hw(P, Q, pad=1):
+    """Output size of MaxPool(3, 2, pad) over a P x Q map."""
+    return (P + 2 * pad - 3) // 2 + 1, (Q + 2 * pad - 3) // 2 + 1
+
+
+def stem_tail_operands(N, P, Q, layer, dtype, C=64, seed=0, pad=1):
+    """``stem32_tail_operands`` for the 16-bit kernels and MaxPool(3, 2, ``pad``): y and dp are rounded to ``dtype`` (the
+    values the kernels read, held as ``dtype`` tensors), and about a tenth of the argmax bytes carry the dead code 255
+    (a window whose maximum is the ReLU's zero) next to the codes 0..8, which at pad 1 include positions outside the
+    image.  Layer B scales channel 1 of dp, of the scale and of the shift by 1e-3: a small channel cannot hide in a
+    norm.  The fp32 operands of ``stem32_tail_operands`` are untouched by this function."""
+    OH, OW = pool_out_hw(P, Q, pad)
+    d = stem32_tail_operands(N, P, Q, layer, C=C, seed=seed + 1000 * pad + (7 if dtype == torch.float16 else 0))
+    gen = torch.Generator().manual_seed(79 + 13 * P + Q + C + seed + 1000 * pad)
+    idx = torch.randint(0, 9, (N, OH, OW, C), generator=gen, dtype=torch.uint8)
+    idx[torch.rand(N, OH, OW, C, generator=gen) < 0.1] = 255
+    if layer == "int":
+        dp = nm.conv_int_operands((N, OH, OW, C), XVALS, 74 + P + seed + pad)
+    else:
+        dp = torch.randn(N, OH, OW, C, generator=gen)
+        dp[..., 1] *= 1e-3
+        d["coef"][1] *= 1e-3
+        d["coef"][C + 1] *= 1e-3
+    return dict(y=d["y"].to(dtype), dp=dp.to(dtype), idx=idx, coef=d["coef"].contiguous(), b=d["b"])
+
+
+# ResNet stem weight gradient in window mode, (T, U) = (4, 1): images (N, H, W).  Plain kernel: an odd conv height and
+# width / even ones / a multiple of 4 x 16; fused raw-row kernel: conv output a multiple of 4 x 16; fused quad kernel:
+# an odd conv height (half-dead last quads), a pooled width whose last window column is missing, both
+STEM_WGRAD_PLAIN = [(2, 29, 28), (3, 28, 36), (5, 32, 32)]
+STEM_WGRAD_ROWS = [(2, 8, 32), (5, 32, 32)]
+STEM_WGRAD_QUAD = [(2, 29, 28), (3, 28, 36), (5, 29, 36)]
+
+
+def stem_fused_operands(N, H, W, dtype, layer):
+    """Operands of the fused stem weight gradient: dict x (fp32 NCHW image), y (stand-in conv output [N, P, Q, 64]), dp,
+    coef, b as ``stem_tail_operands`` makes them, and idx CONSISTENT with y, as bn_relu_maxpool writes it (the fused
+    kernels take the ReLU mask from it): the first fp64 argmax of each window, 255 where the maximum is 0; on top a
+    tenth of the windows are marked dead and a tenth of the top-row windows carry a code of the row above the image --
+    neither routes a gradient, in the kernels or in ``stem_tail_ref``."""
+    import _pool_cases as pc
+    P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    d = stem_tail_operands(N, P, Q, layer, dtype, C=64, seed=H + W)
+    r = pc.pool_fwd_ref(d["y"], d["coef"], 3, 1)
+    idx = torch.where(r["ref"] > 0, r["first"], torch.full_like(r["first"], 255)).to(torch.uint8)
+    gen = torch.Generator().manual_seed(83 + H * W)
+    idx[torch.rand(idx.shape, generator=gen) < 0.1] = 255
+    top = torch.rand(idx[:, 0].shape, generator=gen) < 0.1
+    idx[:, 0] = torch.where(top, torch.randint(0, 3, idx[:, 0].shape, generator=gen, dtype=torch.uint8), idx[:, 0])
+    x = nm.conv_int_operands((N, 3, H, W), XVALS, 84 + H) if layer == "int" else torch.randn(N, 3, H, W, generator=gen)
+    return dict(d, idx=idx, x=x)
+
+
+def stem_tail_ref(d, N, P, Q, C, pad=1):
+    """Independent fp64 reference of the stem's backward tail from ``stem32_tail_operands`` / ``stem_tail_operands``
+    (any device; MaxPool(3, 2, ``pad``)): the pooled gradient scattered along the argmax bytes (the dead code 255 and
+    codes pointing outside the image select nothing), the ReLU mask from
     y*scale + shift, dY = A*dz + B*y + Cc.  Returns dict dz, dzmag (scatter of |dp|), unsure (|pre| <= 8u*mag: the sign
     fp32 may call either way), dy, dymag (|A|*dzmag + |B*y| + |Cc|), dyflip (|A|*dzmag where unsure, else 0)."""
     y, dp, idx = d["y"], d["dp"], d["idx"]
     dev = y.device
-    OH, OW = (P - 1) // 2 + 1, (Q - 1) // 2 + 1
+    OH, OW = pool_out_hw(P, Q, pad)
     dz = torch.zeros(N, P, Q, C, dtype=torch.float64, device=dev)
     dzmag = torch.zeros_like(dz)
     n_i, oh_i, ow_i, c_i = torch.meshgrid(*[torch.arange(s, device=dev) for s in (N, OH, OW, C)], indexing="ij")
-    h = oh_i * 2 - 1 + (idx // 3).long()
-    w = ow_i * 2 - 1 + (idx % 3).long()
-    ok = (h >= 0) & (h < P) & (w >= 0) & (w < Q)
+    h = oh_i * 2 - pad + (idx // 3).long()
+    w = ow_i * 2 - pad + (idx % 3).long()
+    ok = (idx < 9) & (h >= 0) & (h < P) & (w >= 0) & (w < Q)
     flat = ((n_i * P + h) * Q + w) * C + c_i
     dz.view(-1).index_put_((flat[ok],), dp.double()[ok], accumulate=True)
     dzmag.view(-1).index_put_((flat[ok],), dp.double().abs()[ok], accumulate=True)

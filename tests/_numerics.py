@@ -71,6 +71,16 @@ Convolutions on the fp32 MFMA (v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accum
   half of the ``k = 8`` elementwise budget and 7 more than a stored operand: ``(n + 12) * 2u * mag`` with ``mag`` the
   weight-gradient of ``|x|`` and ``|A|*sum|dp| + |B*y| + |C|``.
 
+* The 16-bit fused stem weight gradients (``wgrad_stem_rows`` / ``wgrad_stem_quad``) form dY = A*dz + B*y + C per 2x2
+  quad in fp32 (dz: up to 4 pooled gradients added in window order, then two fmas: at most 5 roundings per term, inside
+  the ``12u * dymag`` of stem_pool_bwd_apply) and ROUND IT TO 16 BITS (``E::pack2``) into the LDS tile the MFMA reads:
+  the operand is off by ``e_i = half_ulp16(dY_i) + 12u * dymag_i`` from the fp64 dY.  That error is carried through the
+  sum, the accumulation adds the usual term:
+  ``|dw - ref| <= sum_i |x_i| * e_i + (n + 4) * 2u * sum_i |x_i| * (|dY_i| + e_i)`` (``stem_fused_bound``).  The ReLU mask
+  is not recomputed there: it is in the argmax bytes (a dead window carries 255), so the operands' argmax must agree with
+  y (``cc.stem_fused_operands``).  Integer operands: dY is a multiple of 1/2 below 32, exact in both 16-bit types, so
+  the result equals the fp64 reference.
+
 References are fp64 and are computed from the very 16-bit / fp32 values the kernel reads, so no input rounding enters
 the bounds.  ``tests/test_numerics_model_cpu.py`` proves that a plain fp32 evaluation of every formula stays inside its
 bound and that each assertion rejects a one-ulp error, a dropped row and coefficients shifted by one channel.
@@ -381,6 +391,15 @@ def assert_conv(out, ref64, mag64, n, dtype, name, family):
     """Every element of a forward / data-gradient (16-bit) or weight-gradient (``dtype`` float32) result within
     ``conv_bound``; the failure names the element's index (n, h, w, channel)."""
     return assert_within(out, ref64, conv_bound(ref64, mag64, n, dtype), name, ref64.shape[-1], family, ref64.shape)
+
+
+def stem_fused_bound(x, dy64, dymag64, n, dtype):
+    """Element bound [64, 7, 7, 3] of the 16-bit fused stem weight gradient (module docstring): ``x`` the NHWC image the
+    kernel reads, ``dy64`` / ``dymag64`` the fp64 dY [N, P, Q, 64] and the sum of the absolute values of its terms."""
+    e = half_ulp16(dy64, dtype) + 12 * U * dymag64
+    _, carried = conv_wgrad_ref(x, e, 7, 7, 2, 3)
+    _, mag = conv_wgrad_ref(x, dy64.abs() + e, 7, 7, 2, 3)
+    return carried + (n + 4) * 2 * U * mag
 
 
 def conv32_bound(mag64, n, extra=5):

@@ -683,6 +683,199 @@ def test_stem_window_mode(N, blocks_per_cu, dtype, layer):
                        0, 0, 256, 64, 32, 4)
         assert c.n("conv_generic_fwd_window") == 1, c.d
         _check16(y2, k, layer, dtype, "window-mode conv_fwd", "conv16_fwd")
+        # the pair form: one 64-wide K-step covers kernel rows (2t, 2t + 1), 4 steps two image rows apart; the eighth
+        # kernel row and the eighth column are zero weights (n = 4 * 64 terms)
+        wpair = torch.zeros(K, 8, 8, 4, dtype=dtype, device=DEV)
+        wpair[:, :7, :7, :3] = k["wk"]
+        wpair = wpair.reshape(K, 4 * 64).contiguous()
+        kp = dict(k, n=4 * 64)
+        for bm, bn in ((256, 64), (128, 64)):
+            y3 = _nan(N, P, Q, K, dtype=dtype)
+            with _Counts() as c:
+                C.conv_fwd(xp, wpair, y3.view(-1), None, None, N, Hp, Wp, 64, K, 4, 1, P, Q, 2, 2, 0, 0, 2, 0, P, Q, 1, 1,
+                           0, 0, bm, bn, 64, 4)
+            assert c.n("conv_generic_fwd_window") == 1, c.d
+            _check16(y3, kp, layer, dtype, f"window-pair conv_fwd tile {(bm, bn)}", "conv16_fwd")
+
+
+# ============================================================================ the 3-channel first conv (VGG, AlexNet)
+def _first_case(case, dtype, layer):
+    """Operands, the padded NHWC4 image as VGGExecutor._forward sizes it, the production index maps
+    (executor_vgg.first_conv_maps) and the fp64 references from the 16-bit image stem_pack stores."""
+    from pytorch_distributed_template_amd.models.executor_vgg import first_conv_maps
+
+    def make():
+        C = _C()
+        R, st, pad, N, H, W = case
+        P, Q = cc.out_hw(cc.first_conv_geom(case))
+        x, wk, dy = (_dev(t) for t in cc.first_conv_operands(case, dtype, layer))
+        win, gidx, T, U, ldw = first_conv_maps(64, R)
+        Hp, Wp = max(H + 2 * pad, (P - 1) * st + 2 * T), max(W + 2 * pad, (Q - 1) * st + 8 * U)
+        xp = _nan(N * Hp * Wp * 4, dtype=dtype)
+        C.stem_pack(x, xp, N, 3, H, W, pad, Hp, Wp)
+        wwin = _nan(64 * R * U * 32, dtype=dtype)
+        C.gather16(wk.reshape(-1), _dev(win), wwin)
+        xr = x.to(dtype).permute(0, 2, 3, 1).contiguous()  # what stem_pack stores (round to nearest even)
+        ref, mag = nm.conv_fwd_ref(xr, wk, st, pad)
+        wref, wmag = nm.conv_wgrad_ref(xr, dy, R, R, st, pad)
+        return dict(xp=xp, wwin=wwin, dy=dy, gidx=_dev(gidx), geom=(R, st, N, P, Q, Hp, Wp, T, U, ldw),
+                    fwd=dict(ref=ref, mag=mag, n=R * U * 32), wg=dict(ref=wref, mag=wmag, n=N * P * Q))
+    return _cached(("first", case, dtype, layer), make)
+
+
+@pytest.mark.parametrize("layer", LAYERS)
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("stats", [False, True])
+@pytest.mark.parametrize("case", cc.FIRST_CONV)
+def test_first_conv_forward_window_mode(case, stats, dtype, layer):
+    """Window-mode conv_fwd as VGGExecutor._forward calls it: one kernel row per tap row, U 8-pixel windows 8 pixels apart
+    (U = 2: the 11- and 9-wide rows), tile (256, 64, 32), with and without the statistics slots.  The reduction holds
+    R * U * 32 terms (the zero padding of the windows included): n of the bound."""
+    C = _C()
+    k = _first_case(case, dtype, layer)
+    R, st, N, P, Q, Hp, Wp, T, U, ldw = k["geom"]
+    y, sl = _nan(N, P, Q, 64, dtype=dtype), (_slots(C, 64) if stats else None)
+    with _Counts() as c:
+        C.conv_fwd(k["xp"], k["wwin"], y.view(-1), None, sl, N, Hp, Wp, 32, 64, R, U, P, Q, st, st, 0, 0, 1, 8, P, Q, 1, 1,
+                   0, 0, 256, 64, 32, 4)
+    assert c.n("conv_generic_fwd_window") == 1, c.d
+    _check16(y, k["fwd"], layer, dtype, f"first conv {case} fwd", "conv16_fwd")
+    if stats:
+        _check_stats(sl.view(-1, 64, 2).sum(0), y, k["fwd"], layer, dtype, f"first conv {case} fwd")
+
+
+@pytest.mark.parametrize("layer", LAYERS)
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("target", cc.WGRAD_TARGETS)
+@pytest.mark.parametrize("case", cc.FIRST_CONV)
+def test_first_conv_wgrad_window_mode(case, target, dtype, layer):
+    """Window-mode conv_wgrad as VGGExecutor._first_wgrad calls it: T kernel-row pairs 2 rows apart x U 8-pixel windows
+    8 pixels apart, then wgrad_reduce, then the production gather to KRSC.  The kernel's partials (summed in fp64) and
+    the reducer's output are judged separately; the partials of the padding kernel row of an odd R and of the columns
+    past R are finite, and the gather drops them."""
+    C = _C()
+    k = _first_case(case, dtype, layer)
+    R, st, N, P, Q, Hp, Wp, T, U, ldw = k["geom"]
+    splits, pps, _ = C.conv_wgrad_plan(64, T, U, 64, N * P * Q, target, True)
+    ws = _nan(splits * 64 * ldw, dtype=torch.float32)
+    with _Counts() as c:
+        C.conv_wgrad(k["xp"], k["dy"], ws, N, Hp, Wp, 64, 64, T, U, P, Q, st, st, 0, 0, 2, 8, ldw, splits, pps, 4, True)
+    assert c.n("conv_wgrad_window") == 1, c.d
+    assert bool(torch.isfinite(ws).all()), "a partial (padding row / columns included) is not finite or was not written"
+    name = f"first conv {case} wgrad target {target} ({splits} splits)"
+    part = ws.view(splits, -1).double().sum(0)[k["gidx"].long()].view(64, R, R, 3)
+    if layer == "int":
+        nm.assert_exact(part, k["wg"]["ref"].float().double(), f"{name}: partials")
+    else:
+        _rec("conv16_wgrad", dtype, nm.assert_conv(part, k["wg"]["ref"], k["wg"]["mag"], k["wg"]["n"], torch.float32,
+                                                   f"{name}: partials", "conv16_wgrad"))
+    tmp = _nan(64 * ldw, dtype=torch.float32)
+    C.wgrad_reduce(ws, splits, 64, ldw, ldw, 64 * ldw, tmp, ldw, 1.0, False)
+    assert bool(torch.isfinite(tmp).all())
+    dw = _nan(64 * R * R * 3, dtype=torch.float32)
+    C.gather32(tmp, k["gidx"], dw)
+    _check_wgrad(dw.view(64, R, R, 3), k["wg"], layer, name, dtype)
+
+
+# ============================================================================ ResNet stem weight gradient, (T, U) = (4, 1)
+def _stem_wgrad_case(nhw, dtype, layer):
+    """The padded image, the tail operands with an argmax consistent with y, the independent fp64 dY
+    (cc.stem_tail_ref) and the references of the plain (16-bit dY operand) and the fused weight gradient."""
+    from pytorch_distributed_template_amd.models.executor_vgg import first_conv_maps
+
+    def make():
+        C = _C()
+        N, H, W = nhw
+        P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        d = {k: _dev(v) for k, v in cc.stem_fused_operands(N, H, W, dtype, layer).items()}
+        r = cc.stem_tail_ref(d, N, P, Q, 64)
+        _, gidx, T, U, ldw = first_conv_maps(64, 7)
+        assert (T, U, ldw) == (4, 1, 256)
+        Hp, Wp = max(H + 6, 2 * (P - 1) + 8), max(W + 6, 2 * (Q - 1) + 8)
+        xp = _nan(N * Hp * Wp * 4, dtype=dtype)
+        C.stem_pack(d["x"], xp, N, 3, H, W, 3, Hp, Wp)
+        xr = d["x"].to(dtype).permute(0, 2, 3, 1).contiguous()
+        n = N * P * Q
+        # plain kernel: dY is an operand -- the reference dY rounded to the dtype (integer layer: unchanged)
+        dy16 = r["dy"].float().to(dtype)
+        pref, pmag = nm.conv_wgrad_ref(xr, dy16, 7, 7, 2, 3)
+        fref, fmag = nm.conv_wgrad_ref(xr, r["dy"], 7, 7, 2, 3)
+        if layer == "int":  # dY representable, every partial sum (in units of 1/2) below 2**24
+            assert bool((nm.round_exact(r["dy"], dtype) == r["dy"]).all()) and 2 * float(fmag.max()) < 2.0 ** 24
+            fbound = None
+        else:
+            fbound = nm.stem_fused_bound(xr, r["dy"], r["dymag"], n, dtype)
+        return dict(d=d, xp=xp, dy16=dy16, gidx=_dev(gidx), geom=(N, P, Q, Hp, Wp), plain=dict(ref=pref, mag=pmag, n=n),
+                    fref=fref, fbound=fbound)
+    return _cached(("stem_wgrad", nhw, dtype, layer), make)
+
+
+def _stem_plans(total):
+    """Split plans over ``total`` (quad-padded) pixels: one split, the planner's for many blocks, 384-pixel splits (a
+    ragged last one wherever total is no multiple of 384)."""
+    splits, pps, _ = _C().conv_wgrad_plan(64, 4, 1, 64, total, 2048, True)
+    if splits * pps < total:
+        pps = (-(-total // splits) + 127) // 128 * 128
+    return sorted({(1, (total + 127) // 128 * 128), (splits, pps), (-(-total // 384), 384)})
+
+
+def _stem_judge(ws, splits, k, layer, dtype, name, fused):
+    """The partials (fp64 sum) and wgrad_reduce's output, each gathered to KRSC through the production map."""
+    C = _C()
+    assert bool(torch.isfinite(ws).all()), f"{name}: a partial is not finite or was not written"
+    tmp = _nan(64 * 256, dtype=torch.float32)
+    C.wgrad_reduce(ws, splits, 64, 256, 256, 64 * 256, tmp, 256, 1.0, False)
+    dw = _nan(64 * 7 * 7 * 3, dtype=torch.float32)
+    C.gather32(tmp, k["gidx"], dw)
+    part = ws.view(splits, -1).double().sum(0)[k["gidx"].long()]
+    for what, got in (("partials", part), ("reduced", dw)):
+        got = got.view(64, 7, 7, 3)
+        if not fused:
+            _check_wgrad(got.float(), k["plain"], layer, f"{name}: {what}", dtype)
+        elif layer == "int":
+            nm.assert_exact(got, k["fref"].float().double(), f"{name}: {what}")
+        else:
+            _rec("conv16_stem_fused", dtype, nm.assert_within(got, k["fref"], k["fbound"], f"{name}: {what}", 3,
+                                                              "conv16_stem_fused", k["fref"].shape))
+
+
+@pytest.mark.parametrize("layer", LAYERS)
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("nhw", cc.STEM_WGRAD_PLAIN)
+def test_stem_wgrad_plain(nhw, dtype, layer):
+    """wgrad_stem: the 7x7/2 weight gradient over the padded NHWC4 image with dY as a 16-bit operand, every split plan."""
+    C = _C()
+    k = _stem_wgrad_case(nhw, dtype, layer)
+    N, P, Q, Hp, Wp = k["geom"]
+    for splits, pps in _stem_plans(N * P * Q):
+        ws = _nan(splits * 64 * 256, dtype=torch.float32)
+        with _Counts() as c:
+            C.conv_wgrad(k["xp"], k["dy16"], ws, N, Hp, Wp, 64, 64, 4, 1, P, Q, 2, 2, 0, 0, 2, 2, 256, splits, pps, 4, True)
+        assert c.n("wgrad_stem") == 1 and c.n("wgrad_stem_fused") == 0, c.d
+        _stem_judge(ws, splits, k, layer, dtype, f"wgrad_stem {nhw} ({splits} x {pps})", False)
+
+
+@pytest.mark.parametrize("layer", LAYERS)
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("kernel,nhw", [("wgrad_stem_rows", g) for g in cc.STEM_WGRAD_ROWS] +
+                         [("wgrad_stem_quad", g) for g in cc.STEM_WGRAD_QUAD])
+def test_stem_wgrad_fused_dy_per_element(kernel, nhw, dtype, layer):
+    """The fused stem weight gradients (dY = A*dz + B*y + C formed per 2x2 quad in the kernel and rounded to 16 bits before
+    the MFMA) against the independent fp64 dY of cc.stem_tail_ref -- never against the two-pass path: ``int`` bit-exact,
+    ``real`` within nm.stem_fused_bound.  The raw-row kernel needs a conv output of 4k x 16k pixels, every other shape
+    runs the quad kernel (an odd height: half-dead last quads)."""
+    C = _C()
+    k = _stem_wgrad_case(nhw, dtype, layer)
+    d = k["d"]
+    N, P, Q, Hp, Wp = k["geom"]
+    assert (P % 4 == 0 and Q % 16 == 0) == (kernel == "wgrad_stem_rows")
+    for splits, pps in _stem_plans(N * ((P + 1) // 2) * 2 * Q):
+        ws = _nan(splits * 64 * 256, dtype=torch.float32)
+        with _Counts() as c:
+            C.conv_wgrad_stem_fused(k["xp"], d["dp"], d["idx"], d["y"], d["coef"], d["b"], ws, N, Hp, Wp, 4, P, Q, 2, 2, 256,
+                                    splits, pps)
+        assert c.n("wgrad_stem_fused") == 1 and c.n("wgrad_stem_rows") == (1 if kernel == "wgrad_stem_rows" else 0), c.d
+        _stem_judge(ws, splits, k, layer, dtype, f"{kernel} {nhw} ({splits} x {pps})", True)
 
 
 # ============================================================================ weight gradients
@@ -703,6 +896,54 @@ def _wgrad_route(g, target, dtype, layer, plan_tile, counter):
 @pytest.mark.parametrize("g", cc.WGRAD_GENERIC)
 def test_wgrad_generic_64x64(g, target, dtype, layer):
     _wgrad_route(g, target, dtype, layer, 64, "conv_wgrad_generic")
+
+
+def _tile_counter(tile, g):
+    """The counter of the kernel the planner's tile names."""
+    if tile == 256:
+        return "conv_wgrad_pp"
+    if tile == 2:
+        return "conv_wgrad_wide" if cc.out_hw(g)[1] >= 4 else "conv_wgrad_generic"
+    if tile == 128:
+        return "conv_wgrad_128_pair" if g[3] == 64 else "conv_wgrad_128"
+    return "conv_wgrad_generic"
+
+
+@pytest.mark.parametrize("layer", LAYERS)
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("target", cc.WGRAD_TARGETS)
+@pytest.mark.parametrize("g", cc.WGRAD_ALEXNET)
+def test_wgrad_alexnet_shapes_on_the_planners_tile(g, target, dtype, layer):
+    N, H, W, Ci, K, R, st, pad = g
+    P, Q = cc.out_hw(g)
+    tile = _C().conv_wgrad_plan(K, R, R, Ci, N * P * Q, target, False)[2]
+    _wgrad_route(g, target, dtype, layer, tile, _tile_counter(tile, g))
+
+
+@pytest.mark.parametrize("layer", LAYERS)
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("target", cc.WGRAD_TARGETS)
+@pytest.mark.parametrize("g", cc.WGRAD_CLASSIFIER)
+def test_wgrad_classifier_with_cropped_reduce(g, target, dtype, layer):
+    """The classifier's weight gradient: a 1x1 conv over H = W = 1 (5 and 130 pixels in all), then wgrad_reduce over
+    rows = cout - 28 with ldo = cols: the rows it owns hold the gradient, the rows beyond stay untouched (NaN)."""
+    C = _C()
+    N, H, W, Ci, K, R, st, pad = g
+    k = _wgrad_case(g, dtype, layer)
+    splits, pps, tile = C.conv_wgrad_plan(K, 1, 1, Ci, N, target, False)
+    ws = _nan(splits * K * Ci, dtype=torch.float32)
+    with _Counts() as c:
+        C.conv_wgrad(k["x"], k["dy"], ws, N, 1, 1, Ci, K, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, Ci, splits, pps, 0, False)
+    assert c.n(_tile_counter(tile, g)) == 1, c.d
+    name = f"classifier wgrad {g} target {target} ({splits} splits)"
+    part = dict(k, ref=k["ref"].view(K, Ci), mag=k["mag"].view(K, Ci))
+    _check_wgrad(ws.view(splits, K, Ci).double().sum(0).float(), part, layer, f"{name}: partials", dtype)
+    rows = K - 28
+    out = _nan(K, Ci, dtype=torch.float32)
+    C.wgrad_reduce(ws, splits, rows, Ci, Ci, K * Ci, out, Ci, 1.0, False)
+    crop = dict(k, ref=k["ref"].view(K, Ci)[:rows], mag=k["mag"].view(K, Ci)[:rows])
+    _check_wgrad(out[:rows], crop, layer, name, dtype)
+    assert bool(torch.isnan(out[rows:]).all()), f"{name}: wgrad_reduce wrote beyond its rows"
 
 
 @pytest.mark.parametrize("layer", LAYERS)

@@ -240,6 +240,9 @@ def _ref_of(kind, g, dtype, layer, opt):
     if kind == "stem":
         x, wk = cc.stem_operands(g[0], g[1], g[2], dtype, layer)
         return nm.conv_fwd_ref(x.to(dtype).permute(0, 2, 3, 1), wk, 2, 3) + (64,)
+    if kind == "first":
+        x, wk, _ = cc.first_conv_operands((g[5], g[6], g[7], g[0], g[1], g[2]), dtype, layer)
+        return nm.conv_fwd_ref(x.to(dtype).permute(0, 2, 3, 1), wk, g[6], g[7]) + (64,)
     if kind.startswith("grouped"):
         _, _, full = cc.grouped_weights(g[3], opt["groups"], dtype, layer)
         if kind == "grouped_fwd":
@@ -931,3 +934,389 @@ def test_real_bound_at_32_terms_rejects_11_bit_operands_and_long_reductions_do_n
     ref, mag = nm.conv_fwd_ref(x, w, 1, 1)
     r8, _ = nm.conv_fwd_ref(nm.round_to_bits(x, 8), nm.round_to_bits(w, 8), 1, 1)
     nm.assert_conv32(r8, ref, mag, 4608, "8-bit operands at n = 4608", None)
+
+
+# ======================================================================= the 16-bit pools and stem tail (pool.hip)
+# tests/test_stem_tail_numerics_gpu.py runs these assertions on the kernels; here a plain fp32 evaluation must pass them
+# and the listed mutations must fail, and the conditions on the operands are checked from the references alone.
+import _pool_cases as pc  # noqa: E402
+
+POOL_SHAPES = [(1, 2, 12, 11, 64), (1, 2, 13, 11, 8), (0, 2, 13, 11, 64), (0, 2, 12, 10, 8), (0, 1, 3, 3, 8),
+               (0, 1, 4, 4, 16), (0, 3, 27, 27, 192)]
+TAIL_SHAPES = [(2, 12, 11, 64), (2, 13, 11, 64), (2, 55, 55, 64), (1, 3, 5, 64), (2, 13, 11, 8)]
+
+
+def _tail_emul(d, N, P, Q, C, pad, dtype):
+    """Plain fp32 evaluation of the backward tail: (dz of maxpool_bwd_relu, dY of stem_pool_bwd_apply, the [C, 2] sums of
+    stem_pool_bwd_reduce), the first two rounded once to ``dtype``."""
+    OH, OW = cc.pool_out_hw(P, Q, pad)
+    idx = d["idx"]
+    n_i, oh_i, ow_i, c_i = torch.meshgrid(*[torch.arange(s) for s in (N, OH, OW, C)], indexing="ij")
+    h, w = oh_i * 2 - pad + (idx // 3).long(), ow_i * 2 - pad + (idx % 3).long()
+    ok = (idx < 9) & (h >= 0) & (h < P) & (w >= 0) & (w < Q)
+    acc = torch.zeros(N * P * Q * C)
+    acc.index_put_(((((n_i * P + h) * Q + w) * C + c_i)[ok],), d["dp"].float()[ok], accumulate=True)
+    yf = d["y"].float()
+    coef, b = d["coef"], d["b"]
+    dz = torch.where(yf * coef[:C] + coef[C:2 * C] > 0, acc.view(N, P, Q, C), torch.zeros(()))
+    dy = b[:C] * dz + b[C:2 * C] * yf + b[2 * C:3 * C]
+    xh = (yf - coef[2 * C:3 * C]) * coef[3 * C:4 * C]
+    sums = torch.stack([dz.reshape(-1, C).sum(0), (dz * xh).reshape(-1, C).sum(0)], 1)
+    return dz.to(dtype), dy.to(dtype), sums.double()
+
+
+def _bump(t, ref, ok=None, exact=False):
+    """``t`` with one element moved by one 16-bit ulp away from the reference: an element in the lower part of its binade
+    (where one ulp is furthest above the half-ulp bound), as test_assert_rounded_rejects_one_element_off_by_one_ulp does;
+    None where the case has no such element."""
+    frac = torch.frexp(ref.abs().float())[0].flatten()
+    pick = (frac > 0.5) & (frac < 0.6) & (ref.abs().flatten() > 2.0 ** -10)
+    if exact:  # a zero bound: any element will do
+        pick = ref.flatten() != 0
+    if ok is not None:
+        pick &= ok.flatten()
+    if not bool(pick.any()):
+        return None
+    i = int(pick.nonzero()[0])
+    bad = t.clone().flatten()
+    bits = bad.view(torch.int16)
+    up = float((bits[i:i + 1] + 1).view(t.dtype).double().item())
+    down = float((bits[i:i + 1] - 1).view(t.dtype).double().item())
+    r = float(ref.flatten()[i].item())
+    bits[i] += 1 if abs(up - r) > abs(down - r) else -1
+    return bad.view_as(t)
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("pad,N,H,W,C", POOL_SHAPES)
+def test_fp32_emulation_of_the_pool_forward_passes_and_mutations_fail(pad, N, H, W, C, dtype):
+    d = cc.stem_tail_operands(N, H, W, "real", dtype, C=C, pad=pad)
+    r = pc.pool_fwd_ref(d["y"], d["coef"], 3, pad)
+    out, idx = pc.pool_fwd_emul(d["y"], d["coef"], dtype, 3, pad, 255)
+    assert pc.assert_pool_fwd(out, idx, r, dtype, 255, "emulation") <= 1.0
+    bad = _bump(out, r["ref"])
+    assert bad is not None or out.numel() <= 64
+    if bad is not None:
+        with pytest.raises(AssertionError, match="out"):
+            pc.assert_pool_fwd(bad, idx, r, dtype, 255, "one ulp")
+    # a dropped window member: the maximum without each window's first maximal member
+    drop = r["win"].clone()
+    drop.scatter_(-1, r["first"].unsqueeze(-1), -1.0)
+    with pytest.raises(AssertionError, match="out"):
+        pc.assert_pool_fwd(drop.max(-1).values.clamp_min(0).to(dtype), idx, r, dtype, 255, "dropped member")
+    # an argmax shifted by one position in a decisive window
+    live = r["decisive"].nonzero()
+    if live.shape[0]:
+        at = tuple(live[0].tolist())
+        bad = idx.clone()
+        bad[at] = (int(idx[at]) + 1) % 9
+        with pytest.raises(AssertionError):
+            pc.assert_pool_fwd(out, bad, r, dtype, 255, "argmax + 1")
+    # coefficients shifted by one channel
+    rolled = torch.cat([d["coef"][:C].roll(1), d["coef"][C:2 * C].roll(1), d["coef"][2 * C:]])
+    o2, i2 = pc.pool_fwd_emul(d["y"], rolled, dtype, 3, pad, 255)
+    with pytest.raises(AssertionError):
+        pc.assert_pool_fwd(o2, i2, r, dtype, 255, "channel + 1")
+    # a live window marked dead, a dead one marked live
+    for mask, code in ((r["must_live"], 255), (r["must_dead"], 4)):
+        hit = mask.nonzero()
+        if hit.shape[0]:
+            bad = idx.clone()
+            bad[tuple(hit[0].tolist())] = code
+            with pytest.raises(AssertionError):
+                pc.assert_pool_fwd(out, bad, r, dtype, 255, "dead code")
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("pad,N,H,W,C", POOL_SHAPES)
+def test_decisive_pool_planes_pin_every_output_and_argmax(pad, N, H, W, C, dtype):
+    """The condition of the integer forward test, from the reference alone: every window is decisive or surely dead, the
+    values are exactly representable, and the emulation is exact."""
+    y, coef = pc.decisive_planes(N, H, W, C, H + C + pad)
+    assert bool((y.to(dtype).float() == y).all())
+    r = pc.pool_fwd_ref(y.to(dtype), coef, 3, pad)
+    assert bool((r["decisive"] | r["must_dead"]).all()) and bool(r["must_dead"][..., 5].all()) and bool(r["decisive"].any())
+    assert bool((nm.round_exact(r["ref"], dtype) == r["ref"]).all())
+    out, idx = pc.pool_fwd_emul(y.to(dtype), coef, dtype, 3, pad, 255)
+    pc.assert_pool_fwd(out, idx, r, dtype, 255, "emulation", exact=True)
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+@pytest.mark.parametrize("pad,N,H,W,C", POOL_SHAPES + [(1,) + s for s in TAIL_SHAPES])
+def test_fp32_emulation_of_the_pool_backward_and_stem_tail(pad, N, H, W, C, layer, dtype):
+    """maxpool_bwd_relu (both pads), stem_pool_bwd_apply and stem_pool_bwd_reduce (pad 1): the emulation passes, the
+    unsure share is <= 1 %, the integer layer is exactly representable; one ulp16, a dropped window gradient, argmax
+    bytes shifted by one and coefficients shifted by one channel fail."""
+    exact = layer == "int"
+    d = cc.stem_tail_operands(N, H, W, layer, dtype, C=C, pad=pad)
+    r = cc.stem_tail_ref(d, N, H, W, C, pad)
+    assert float(r["unsure"].double().mean()) <= 0.01
+    dz, dy, sums = _tail_emul(d, N, H, W, C, pad, dtype)
+    OH, OW = cc.pool_out_hw(H, W, pad)
+    n_chain = pc.reduce16_plan(N * OH * OW, C, 4096)[2]
+    if exact:
+        assert not bool(r["unsure"].any())
+        for v in (r["dz"], r["dy"]):
+            assert bool((nm.round_exact(v, dtype) == v).all())
+        assert float(r["dzmag"].reshape(-1, C).sum(0).max()) * 16 < 2 ** 24  # every sum of the reduce, in units of 1/16
+
+    def check(dz_, dy_, sums_, rr, dd):
+        pc.assert_pool_bwd(dz_, rr, dtype, "dz", exact=exact)
+        if pad == 1:
+            pc.assert_tail_apply(dy_, rr, dtype, "dy", exact=exact)
+            pc.assert_tail_reduce(sums_, dd, rr, C, n_chain, "sums", exact=exact)
+
+    check(dz, dy, sums, r, d)
+    bad = _bump(dz, r["dz"], ~r["unsure"], exact)
+    assert bad is not None or dz.numel() <= 256
+    if bad is not None:
+        with pytest.raises(AssertionError):
+            pc.assert_pool_bwd(bad, r, dtype, "one ulp", exact=exact)
+    if pad == 1:
+        with pytest.raises(AssertionError):
+            pc.assert_tail_apply(_bump(dy, r["dy"], ~r["unsure"], exact), r, dtype, "one ulp", exact=exact)
+    # a dropped window gradient / argmax bytes shifted by one / coefficients of the neighbouring channel: the emulation
+    # of the mutated operands against the reference of the true ones
+    drop = dict(d, dp=d["dp"].clone())
+    big = r["dz"].abs().clone()  # the pixel with the largest gradient outside the small channel
+    big[..., 1] = 0
+    n, h, w, c = [int(v) for v in torch.unravel_index(big.argmax(), big.shape)]
+    for oh in range(OH):
+        for ow in range(OW):
+            k = int(d["idx"][n, oh, ow, c])
+            if k < 9 and (oh * 2 - pad + k // 3, ow * 2 - pad + k % 3) == (h, w):
+                drop["dp"][n, oh, ow, c] = 0
+                break
+        else:
+            continue
+        break
+    shifted = dict(d, idx=torch.where(d["idx"] < 9, (d["idx"] + 1) % 9, d["idx"]))
+    rolled = dict(d, coef=d["coef"].view(4, C).roll(1, 1).reshape(-1), b=d["b"].view(3, C).roll(1, 1).reshape(-1))
+    for name, m in (("dropped window", drop), ("argmax + 1", shifted), ("channel + 1", rolled)):
+        mdz, mdy, msums = _tail_emul(m, N, H, W, C, pad, dtype)
+        if name != "channel + 1" or not exact or bool((mdz.double() != r["dz"]).any()):
+            with pytest.raises(AssertionError):
+                pc.assert_pool_bwd(mdz, r, dtype, name, exact=exact)
+        if pad == 1:
+            with pytest.raises(AssertionError):
+                pc.assert_tail_apply(mdy, r, dtype, name, exact=exact)
+            with pytest.raises(AssertionError):
+                pc.assert_tail_reduce(msums, d, r, C, n_chain, name, exact=exact)
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("k,pad,N,H,W,C", [(3, 1, 2, 12, 11, 64), (3, 1, 2, 13, 11, 8), (3, 0, 2, 13, 11, 64),
+                                           (3, 0, 3, 27, 27, 192), (2, 0, 3, 12, 10, 64)])
+def test_fp32_emulation_of_the_pooled_reduce_link(k, pad, N, H, W, C, dtype):
+    """The pooled reduce's formula in plain fp32 from the emulated 16-bit ``out`` agrees with the sums over the true y
+    at the argmax within the link bound, and with ``out`` of the neighbouring window it fails."""
+    d = cc.stem_tail_operands(N, H, W, "real", dtype, C=C, pad=pad, seed=5)
+    OH, OW = pc.out_hw(H, W, k, pad)
+    dp = d["dp"] if k == 3 else torch.randn(N, OH, OW, C, generator=torch.Generator().manual_seed(5)).to(dtype)
+    out, idx = pc.pool_fwd_emul(d["y"], d["coef"], dtype, k, pad, 255 if k == 3 else None)
+    ref, mag, carry = pc.pooled_link_ref(d["y"], d["coef"], dp, idx, out, k, pad, dtype)
+    n_chain = pc.reduce16_plan(N * OH * OW, C, 2048)[2]
+
+    def formula(o):
+        c = d["coef"]
+        of = o.float()
+        dz = torch.where(of > 0, dp.float(), torch.zeros(()))
+        xh = ((of - c[C:2 * C]) * (1.0 / c[:C]) - c[2 * C:3 * C]) * c[3 * C:4 * C]
+        return torch.stack([dz.reshape(-1, C).sum(0), (dz * xh).reshape(-1, C).sum(0)], 1).double()
+
+    pc.assert_pooled_link(formula(out), ref, mag, carry, n_chain, "emulation")
+    with pytest.raises(AssertionError):
+        pc.assert_pooled_link(formula(out.roll(1, 2)), ref, mag, carry, n_chain, "neighbouring window")
+
+
+# ------------------------------------------------------------------------------------------------ vgg.hip
+POOL2_SHAPES = [(3, 12, 10, 64), (2, 2, 2, 8), (1, 6, 4, 8), (2, 4, 6, 512), (5, 14, 14, 24)]
+
+
+def _pool2_bwd_emul(d, idx, out, dtype):
+    """Plain fp32 evaluation of maxpool2_bwd, rounded once to ``dtype``."""
+    N, H, W, C = d["y"].shape
+    g = torch.where(out.float() > 0, d["dp"].float(), torch.zeros(()))
+    dz = torch.zeros(N, H, W, C)
+    for k in range(4):
+        dz[:, k >> 1::2, k & 1::2] = torch.where(idx == k, g, torch.zeros(()))
+    if d["b"] is None:
+        return dz.to(dtype)
+    b = d["b"]
+    return (b[:C] * dz + b[C:2 * C] * d["y"].float() + b[2 * C:3 * C]).to(dtype)
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("form,layer", [("bn", "real"), ("bn", "int"), ("bias", "real")])
+@pytest.mark.parametrize("N,H,W,C", POOL2_SHAPES)
+def test_fp32_emulation_of_the_2x2_pool_and_its_backward(N, H, W, C, form, layer, dtype):
+    """The emulation passes the forward rules on the raw operands and, after ``make_decisive`` (no undecisive window is
+    left: checked from the reference alone), the backward bound; the integer layer is exactly representable and fully
+    pinned; one ulp16, a dropped window member, an argmax shifted by one and coefficients shifted by one channel fail."""
+    exact = layer == "int"
+    d = pc.pool2_operands(N, H, W, C, layer, dtype, form)
+    r = pc.pool_fwd_ref(d["y"], d["coef"], 2, 0)
+    out, idx = pc.pool_fwd_emul(d["y"], d["coef"], dtype, 2, 0, None)
+    pc.assert_pool_fwd(out, idx, r, dtype, None, "emulation", exact=exact)
+    d["y"] = pc.make_decisive(d["y"], d["coef"], dtype, 2, 0, seed=H * W + C)
+    r = pc.pool_fwd_ref(d["y"], d["coef"], 2, 0)
+    assert bool(pc.settled(r).all())
+    out, idx = pc.pool_fwd_emul(d["y"], d["coef"], dtype, 2, 0, None)
+    pc.assert_pool_fwd(out, idx, r, dtype, None, "emulation", exact=exact)
+    assert torch.equal(idx.long(), r["first"]) and torch.equal(out.double() > 0, r["ref"] > 0)
+    dz, ref, mag = pc.pool2_bwd_ref(d, r)
+    if exact:
+        assert bool((r["decisive"] | r["must_dead"]).all())
+        for v in (r["ref"], ref):
+            assert bool((nm.round_exact(v, dtype) == v).all())
+
+    def judge(dy):
+        if form == "bias":
+            nm.assert_exact(dy, dz, "dy")
+        elif exact:
+            nm.assert_exact(dy, nm.round_exact(ref, dtype), "dy")
+        else:
+            nm.assert_rounded(dy, ref, mag, dtype, name="dy", C=C)
+
+    judge(_pool2_bwd_emul(d, idx, out, dtype))
+    # forward mutations
+    bad = _bump(out, r["ref"], None, exact)
+    if bad is not None:
+        with pytest.raises(AssertionError, match="out"):
+            pc.assert_pool_fwd(bad, idx, r, dtype, None, "one ulp", exact=exact)
+    drop = r["win"].clone()
+    drop.scatter_(-1, r["first"].unsqueeze(-1), -1.0)
+    if bool((drop.max(-1).values.clamp_min(0) != r["ref"]).any()):
+        with pytest.raises(AssertionError, match="out"):
+            pc.assert_pool_fwd(drop.max(-1).values.clamp_min(0).to(dtype), idx, r, dtype, None, "dropped member",
+                               exact=exact)
+    at = tuple(r["decisive"].nonzero()[0].tolist())
+    shifted = idx.clone()
+    shifted[at] = (int(idx[at]) + 1) % 4
+    with pytest.raises(AssertionError):
+        pc.assert_pool_fwd(out, shifted, r, dtype, None, "argmax + 1", exact=exact)
+    if form == "bn":
+        rolled = torch.cat([d["coef"][:C].roll(1), d["coef"][C:2 * C].roll(1), d["coef"][2 * C:]])
+        o2, i2 = pc.pool_fwd_emul(d["y"], rolled, dtype, 2, 0, None)
+        with pytest.raises(AssertionError):
+            pc.assert_pool_fwd(o2, i2, r, dtype, None, "channel + 1", exact=exact)
+    # backward mutations: an argmax shifted by one in every window; coefficients of the neighbouring channel; one ulp
+    with pytest.raises(AssertionError):
+        judge(_pool2_bwd_emul(d, (idx + 1) % 4, out, dtype))
+    if form == "bn":
+        with pytest.raises(AssertionError):
+            judge(_pool2_bwd_emul(dict(d, b=d["b"].view(3, C).roll(1, 1).reshape(-1)), idx, out, dtype))
+        with pytest.raises(AssertionError):
+            judge(_bump(_pool2_bwd_emul(d, idx, out, dtype), ref, None, exact))
+
+
+def test_vgg_hash_forms_agree_and_match_hand_checked_values():
+    """vgg_hash is the splitmix64 output function of seed + 0x9E3779B97F4A7C15 * (i + 1), upper 32 bits.  With seed 0
+    the elements 0, 1, 2 are the first three outputs of splitmix64 seeded with 0 -- 0xE220A8397B1DCDAF,
+    0x6E789E6AA1B965F4, 0x06C45D188009454F, the published test vector -- whose upper halves are checked here; the
+    first was also followed by hand: z0 = 0x9E3779B97F4A7C15, z0 ^ (z0 >> 30) = 0x9E3779BB07979AF0."""
+    z0 = 0x9E3779B97F4A7C15
+    assert z0 ^ (z0 >> 30) == 0x9E3779BB07979AF0
+    assert [pc.vgg_hash_int(0, i) for i in range(3)] == [0xE220A839, 0x6E789E6A, 0x06C45D18]
+    assert list(pc.vgg_hash_np(0, 3)) == [0xE220A839, 0x6E789E6A, 0x06C45D18]
+    for seed in (0, 11, 2 ** 63 - 1):
+        for start in (0, 2 ** 27 + 5):
+            want = [pc.vgg_hash_int(seed, start + i) for i in range(64)]
+            assert list(pc.vgg_hash_np(seed, 64, start)) == want
+            assert pc.vgg_hash_torch(seed, 64, start, "cpu").tolist() == want
+    assert pc.dropout_consts(2.0 ** -33) == (1, 1.0) and pc.dropout_consts(0.5) == (2 ** 31, 2.0)
+    assert pc.dropout_consts(0.0) == (0, 1.0) and pc.dropout_consts(0.999)[0] == int(0.999 * 2 ** 32)
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+def test_fc_act_reference_is_the_fp32_evaluation_and_rejects_a_shifted_keep_mask(dtype):
+    g = torch.Generator().manual_seed(5)
+    rows, F_, p, seed = 37, 136, 0.1, 11
+    z, bias = torch.randn(rows, F_, generator=g).to(dtype), torch.randn(F_, generator=g) * 0.5
+    thr, scale = pc.dropout_consts(p)
+    keep = torch.from_numpy(pc.vgg_hash_np(seed, rows * F_) >= thr).view(rows, F_)
+    emul = torch.where(keep, torch.relu(z.float() + bias) * scale, torch.zeros(())).to(dtype)
+    nm.assert_exact(emul, pc.fc_act_ref(z, bias, F_, p, keep, dtype), "fc_act_fwd emulation")
+    with pytest.raises(AssertionError):
+        nm.assert_exact(emul, pc.fc_act_ref(z, bias, F_, p, keep.roll(1, 1), dtype), "keep mask + 1")
+    with pytest.raises(AssertionError):
+        nm.assert_exact(emul, pc.fc_act_ref(z, bias.roll(1), F_, p, keep, dtype), "bias + 1")
+    dh = torch.randn(rows, F_, generator=g).to(dtype)
+    dz = torch.where(emul > 0, dh.float() * scale, torch.zeros(())).to(dtype)
+    nm.assert_exact(dz, pc.fc_act_bwd_ref(dh, emul, p, dtype), "fc_act_bwd emulation")
+    with pytest.raises(AssertionError):
+        nm.assert_exact(dz, pc.fc_act_bwd_ref(dh, emul, 0.0, dtype), "scale dropped")
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("layer", ["int", "real"])
+@pytest.mark.parametrize("case", cc.FIRST_CONV)
+def test_first_conv_window_maps_and_weight_gradient_assertion(case, layer, dtype):
+    """The production index maps of the first conv (executor_vgg.first_conv_maps): the forward map lays every weight at
+    window (r, s // 8), element (s % 8) * 4 + c and zero elsewhere; the gradient map reads it back.  A plain fp32
+    weight gradient laid out as the kernel's window tile (padding row and columns filled with finite garbage) and gathered
+    through the map passes the bound (``int``: exact, every sum below 2**24); a dropped kernel row does not."""
+    from pytorch_distributed_template_amd.models.executor_vgg import first_conv_maps
+    R, st, pad, N, H, W = case
+    x, wk, dy = cc.first_conv_operands(case, dtype, layer)
+    win, gidx, T, U, ldw = first_conv_maps(64, R)
+    assert (T, U, ldw) == ((R + 1) // 2, (R + 7) // 8, (R + 1) // 2 * ((R + 7) // 8) * 64)
+    flat = wk.reshape(-1)
+    wwin = torch.where(win >= 0, flat[win.clamp_min(0).long()], torch.zeros((), dtype=dtype)).view(64, R, U, 8, 4)
+    expect = torch.zeros(64, R, U * 8, 4, dtype=dtype)
+    expect[:, :, :R, :3] = wk
+    assert torch.equal(wwin.reshape(64, R, U * 8, 4), expect)
+    xr = x.to(dtype).permute(0, 2, 3, 1).contiguous()
+    ref, mag = nm.conv_wgrad_ref(xr, dy, R, R, st, pad)
+    if layer == "int":
+        assert float(mag.max()) < 2.0 ** 24
+    dw = torch.nn.grad.conv2d_weight(xr.float().permute(0, 3, 1, 2), (64, 3, R, R), dy.float().permute(0, 3, 1, 2),
+                                     stride=st, padding=pad).permute(0, 2, 3, 1).contiguous()  # KRSC, plain fp32
+    tile = torch.full((64, T, U, 2, 8, 4), 7.5)
+    for r in range(R):
+        for s in range(R):
+            tile[:, r // 2, s // 8, r % 2, s % 8, :3] = dw[:, r, s]
+    n = N * ((H + 2 * pad - R) // st + 1) * ((W + 2 * pad - R) // st + 1)
+
+    def judge(t):
+        got = t.reshape(-1)[gidx.long()].view(64, R, R, 3)
+        if layer == "int":
+            nm.assert_exact(got, ref.float().double(), "dw")
+        else:
+            nm.assert_conv(got, ref, mag, n, torch.float32, "dw", None)
+
+    judge(tile)
+    dropped = tile.clone()
+    dropped[:, (R - 1) // 2, :, (R - 1) % 2] = 0  # the last kernel row
+    with pytest.raises(AssertionError):
+        judge(dropped)
+
+
+@pytest.mark.parametrize("dtype", cc.DTYPES)
+@pytest.mark.parametrize("nhw", [(2, 29, 28), (2, 8, 32)])
+def test_fp32_emulation_of_the_16_bit_fused_stem_weight_gradient(nhw, dtype):
+    """dY in plain fp32, rounded to the dtype, then a plain fp32 conv2d_weight: inside nm.stem_fused_bound; the argmax
+    of ``cc.stem_fused_operands`` is consistent with y (no routed gradient meets a non-positive pre-activation); dY of
+    the neighbouring channel's coefficients is outside.  The integer layer's dY is representable and its sums exact."""
+    N, H, W = nhw
+    P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    for layer in ("int", "real"):
+        d = cc.stem_fused_operands(N, H, W, dtype, layer)
+        r = cc.stem_tail_ref(d, N, P, Q, 64)
+        assert float((r["dzraw"] - r["dz"]).abs().max()) == 0.0
+        xr = d["x"].to(dtype).permute(0, 2, 3, 1).contiguous()
+        ref, mag = nm.conv_wgrad_ref(xr, r["dy"], 7, 7, 2, 3)
+
+        def emul(b):
+            dy = (b[:64] * r["dzraw"].float() + b[64:128] * d["y"].float() + b[128:192]).to(dtype)
+            return torch.nn.grad.conv2d_weight(xr.float().permute(0, 3, 1, 2), (64, 3, 7, 7), dy.float().permute(0, 3, 1, 2),
+                                               stride=2, padding=3).permute(0, 2, 3, 1)
+        if layer == "int":
+            assert bool((nm.round_exact(r["dy"], dtype) == r["dy"]).all()) and 2 * float(mag.max()) < 2.0 ** 24
+            nm.assert_exact(emul(d["b"]), ref.float().double(), "emulation")
+            continue
+        bound = nm.stem_fused_bound(xr, r["dy"], r["dymag"], N * P * Q, dtype)
+        nm.assert_within(emul(d["b"]), ref, bound, "emulation", 3, f"cpu_plain_conv16_stem_fused/{str(dtype).split('.')[-1]}")
+        with pytest.raises(AssertionError):
+            nm.assert_within(emul(d["b"].view(3, 64).roll(1, 1).reshape(-1)), ref, bound, "channel + 1", 3)

@@ -1,5 +1,5 @@
 """The small loss, pooling and layout kernels called directly, per element against fp64: xent / xent32, metrics,
-colsum32, avgpool_fwd / avgpool_bwd / avgpool32_*, nhwc_nchw16, im2col / im2col32.
+colsum / colsum32, avgpool_fwd / avgpool_bwd / avgpool32_*, nhwc_nchw16, im2col / im2col32.
 
 Bounds (u = 2**-24, tests/_numerics.py):
 
@@ -9,7 +9,7 @@ Bounds (u = 2**-24, tests/_numerics.py):
   involved holds all of that; torch's own fp32 cross_entropy is asserted to stay inside the same bound.
 * xent dlogits: half a 16-bit ulp at |ref| + 2**-18 * gs with gs = loss_scale / grad_div (softmax probabilities are
   at most 1, their relative error is the exponent's absolute error).
-* metrics / colsum32: assert_sum with the kernel's chain length.
+* metrics / colsum / colsum32: assert_sum with the kernel's chain length.
 * avgpool forward: half a 16-bit ulp + (HW + 2) * u * sum|x| / HW (a chain of HW additions, the rounded 1 / HW and the
   product); backward: half a 16-bit ulp + 2u|ref|.
 * layout kernels: exact.
@@ -169,6 +169,28 @@ def test_colsum32(B, ld, ncols):
     d64 = d[:, :ncols].double()
     nm.assert_sum(out[:ncols], s32 * d64.sum(0), abs(s32) * d64.abs().sum(0), math.ceil(B / 4) + 3,
                   f"colsum32 {(B, ld, ncols)}", family="3 colsum32")
+    assert bool((out[ncols:] == -7.5).all())
+
+
+@pytest.mark.parametrize("dtype", DT3[:2], ids=DT3_IDS[:2])
+@pytest.mark.parametrize("B,ld,ncols", [(1200, 1024, 1000), (37, 1024, 1000), (5, 130, 130), (64, 136, 128)])
+def test_colsum16(B, ld, ncols, dtype):
+    """The 16-bit colsum per element at test_colsum32's shapes: ncols % 8 == 0 and ld % 8 == 0 run the 16-byte kernel (32
+    row lanes of ceil(B / 32) additions, 31 to combine them), (5, 130, 130) the scalar one (4 lanes, 3 to combine); the
+    16-bit inputs are exact in fp32 and the output is fp32.  Columns >= ncols are not read (NaN), out beyond ncols is not
+    written."""
+    torch.manual_seed(B + ncols)
+    scale = 0.37
+    d = _nan(B, ld, dtype=dtype)
+    d[:, :ncols] = torch.randn(B, ncols, device=DEV).to(dtype)
+    d[:, 1] *= 1e-3  # a column of small magnitude cannot hide in a norm
+    out = torch.full((ncols + 3,), -7.5, device=DEV)
+    _C().colsum(d, B, ld, ncols, out, scale)
+    s32 = float(torch.tensor(scale, dtype=torch.float32))
+    d64 = d[:, :ncols].double()
+    n_chain = math.ceil(B / 32) + 31 if ncols % 8 == 0 and ld % 8 == 0 else math.ceil(B / 4) + 3
+    nm.assert_sum(out[:ncols], s32 * d64.sum(0), abs(s32) * d64.abs().sum(0), n_chain, f"colsum {(B, ld, ncols)} {dtype}",
+                  family=f"3 colsum16 {str(dtype).split('.')[-1]}")
     assert bool((out[ncols:] == -7.5).all())
 
 
