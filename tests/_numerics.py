@@ -81,6 +81,17 @@ Convolutions on the fp32 MFMA (v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accum
   y (``cc.stem_fused_operands``).  Integer operands: dY is a multiple of 1/2 below 32, exact in both 16-bit types, so
   the result equals the fp64 reference.
 
+* fp16 SUBNORMAL operands (|v| < 2**-14; they occur in unscaled fp16 gradients) lower the accuracy of the MFMA's own
+  sum: the unit aligns the products of one instruction by the operands' exponent FIELDS, and a subnormal's field says
+  2**-14 whatever its leading zeros, so a term is kept to one fp32 ulp of the largest NOMINAL product
+  ``max(|x|, 2**-14) * max(|dy|, 2**-14)``, not of the largest true one (measured on the MI355X through ``conv_wgrad`` with
+  12-term sums: x ~ N(0, 1) against dY ~ 2**-16 * N(0, 1) errs by up to 1.9 * 2u * mag where normal operands give
+  0.9 and bf16 0.5; single products are exact at every exponent pair, nothing is flushed).  The model for a sum with
+  fp16 operands that may be subnormal is therefore the same ``(n + 4) * 2u * mag`` with ``mag`` taken over the nominal
+  magnitudes (``conv_wgrad_nominal_mag``; a zero -- padding included -- counts as 2**-14 too: its field is the same).
+  Normal operands have nominal = true magnitude: the bound is unchanged for them, and bf16 has no subnormals in range.
+  Only the fp32-output weight gradient can see the difference; a 16-bit output's own rounding (at least 2**-25) hides it.
+
 References are fp64 and are computed from the very 16-bit / fp32 values the kernel reads, so no input rounding enters
 the bounds.  ``tests/test_numerics_model_cpu.py`` proves that a plain fp32 evaluation of every formula stays inside its
 bound and that each assertion rejects a one-ulp error, a dropped row and coefficients shifted by one channel.
@@ -260,6 +271,85 @@ def check_bwd_finalize(bcoef, dgamma, dbeta, ref, C, name, family=None):
     return w
 
 
+def xent_ref(logits, bias, tgt, ncls, gs, dtype):
+    """fp64 reference of the fused cross entropy over the first ``ncls`` columns of the 16-bit (or fp32) ``logits``
+    [B, ld] (bounds: tests/test_small_kernels_gpu.py docstring): dict v (logit + bias) and vmag, loss and loss_bound per
+    row, dlogits = (softmax - onehot) * gs and dlogits_bound, correct (first maximum of the fp32 logit + bias == target)."""
+    l64 = logits[:, :ncls].double()
+    b64 = bias.double() if bias is not None else torch.zeros(ncls, dtype=torch.float64, device=logits.device)
+    v64 = l64 + b64
+    loss = F.cross_entropy(v64, tgt, reduction="none")
+    d = (torch.softmax(v64, 1) - F.one_hot(tgt, ncls)) * gs
+    v32 = logits[:, :ncls].float() + (bias if bias is not None else 0.0)  # the fp32 values the kernel compares
+    ar = torch.arange(ncls, device=logits.device).expand_as(v32)
+    first = torch.where(v32 == v32.max(1, keepdim=True).values, ar, torch.full_like(ar, ncls)).min(1).values
+    return dict(v=v64, vmag=l64.abs() + b64.abs(), loss=loss,
+                loss_bound=2.0 ** -18 * (1 + v64.abs().max(1).values + loss.abs()), dlogits=d,
+                dlogits_bound=half_ulp16(d, dtype) + 2.0 ** -18 * gs, correct=(first == tgt).float())
+
+
+def finalize_carried(ref, ds, dss, count, gamma, eps, momentum):
+    """How far forward-finalize outputs may move when the sums they are made from are off by ``ds`` (sum x) and ``dss``
+    (sum x^2) per channel -- the step audit feeds ``bn_finalize_ref`` the fp64 sums of the stored y, the kernel its own
+    fp32-chained statistics of the same y (``assert_conv_stats``'s allowance).  First principles, no linearisation:
+    mean moves by em = ds/count; the biased variance sum x^2/count - mean^2 by ev = dss/count + 2|mean|em + em^2 (the
+    clamp at 0 is 1-Lipschitz); invstd = f(var) = (var + eps)^-1/2 is decreasing and convex, so it moves by at most
+    ei = f(max(var - ev, 0)) - f(var); scale by |gamma| ei; shift = beta - mean * scale by em|scale| + |mean| es + em es;
+    the running statistics' new terms by momentum * em and momentum * ev * count/(count - 1)."""
+    eps32 = float(torch.tensor(eps, dtype=torch.float32).item())
+    mom = float(torch.tensor(momentum, dtype=torch.float32).item())
+    em = ds / count
+    ev = dss / count + 2 * ref["mean"].abs() * em + em * em
+    ei = 1.0 / torch.sqrt((ref["var"] - ev).clamp_min(0.0) + eps32) - ref["invstd"]
+    es = gamma.to(torch.float64).abs() * ei
+    return dict(mean=em, var=ev, invstd=ei, scale=es, shift=em * ref["scale"].abs() + ref["mean"].abs() * es + em * es,
+                rm=mom * em, rv=mom * ev * (count / (count - 1) if count > 1 else 1.0))
+
+
+def check_finalize_carried(coef, rm, rv, ref, car, C, name, family=None):
+    """``check_finalize`` with the statistics' own error ``car`` (``finalize_carried``) carried into every output: each
+    bound is the carried movement e plus the rounding term of ``check_finalize`` taken at |ref| + e."""
+    w = 0.0
+    ab = lambda k: ref[k].abs()
+    w = max(w, assert_within(coef[2 * C:3 * C], ref["mean"], car["mean"] + 2 * U * (ab("mean") + car["mean"]),
+                             f"{name}: mean", C, family))
+    w = max(w, assert_within(coef[3 * C:4 * C], ref["invstd"], car["invstd"] + 4 * U * (ab("invstd") + car["invstd"]),
+                             f"{name}: invstd", C, family))
+    w = max(w, assert_within(coef[:C], ref["scale"], car["scale"] + 4 * U * (ab("scale") + car["scale"]),
+                             f"{name}: scale", C, family))
+    w = max(w, assert_within(coef[C:2 * C], ref["shift"], car["shift"] + 6 * U * (
+        ab("beta") + (ref["mean"] * ref["scale"]).abs() + car["shift"]), f"{name}: shift", C, family))
+    if rm is not None:
+        w = max(w, assert_within(rm, ref["rm_old"] + ref["rm_new"], car["rm"] + 6 * U * (
+            ab("rm_old") + ab("rm_new") + car["rm"]), f"{name}: running_mean", C, family))
+        w = max(w, assert_within(rv, ref["rv_old"] + ref["rv_new"], car["rv"] + 6 * U * (
+            ab("rv_old") + ab("rv_new") + car["rv"]), f"{name}: running_var", C, family))
+    return w
+
+
+def check_bwd_finalize_carried(bcoef, dgamma, dbeta, ref, b0, b1, count, gscale, coef, C, name, family=None):
+    """``check_bwd_finalize`` where the kernel's sums may differ from the reference sums by ``b0`` (sum dz) and ``b1``
+    (sum dz*xhat) per channel (``assert_bnb_sums``'s bounds): dbeta / dgamma move by gscale * b0 / b1; A does not
+    depend on the sums; B = -A*invstd*sdzx/count by |A*invstd| b1/count; Cc = -A*sdz/count + A*invstd*mean*sdzx/count
+    by |A| b0/count + |A*invstd*mean| b1/count.  The rounding terms of ``check_bwd_finalize`` are taken at |ref| + e."""
+    c64 = coef.to(torch.float64)
+    mean, invstd = c64[2 * C:3 * C], c64[3 * C:4 * C]
+    A = ref["A"].abs()
+    eB = A * invstd.abs() * b1 / count
+    eC = A * b0 / count + A * (invstd * mean).abs() * b1 / count
+    w = 0.0
+    if dgamma is not None:
+        e = gscale * b1
+        w = max(w, assert_within(dgamma, ref["dgamma"], e + 2 * U * (ref["dgamma"].abs() + e), f"{name}: dgamma", C, family))
+    if dbeta is not None:
+        e = gscale * b0
+        w = max(w, assert_within(dbeta, ref["dbeta"], e + 2 * U * (ref["dbeta"].abs() + e), f"{name}: dbeta", C, family))
+    w = max(w, assert_within(bcoef[:C], ref["A"], 4 * U * A, f"{name}: bcoef A", C, family))
+    w = max(w, assert_within(bcoef[C:2 * C], ref["B"], eB + 6 * U * (ref["B"].abs() + eB), f"{name}: bcoef B", C, family))
+    w = max(w, assert_within(bcoef[2 * C:3 * C], ref["Cc"], eC + 8 * U * (ref["Cmag"] + eC), f"{name}: bcoef C", C, family))
+    return w
+
+
 def sgd_ref(p, g, buf, wd_mask, lr, momentum, wd, gs, steps):
     """fp64 recurrence of the fused SGD over ``steps`` steps with the fp32 hyper-parameters the kernel receives:
     returns (p, buf, bound) with bound = 6u * sum_steps(|p| + lr|buf|) per element (each step rounds d (3 ops), the
@@ -360,6 +450,28 @@ def conv_wgrad_ref(x, dy, R, S, stride, pad):
         dw = torch.matmul(cols, da).sum(0)  # [C*R*S, K]
         return dw.view(C, R, S, K).permute(3, 1, 2, 0).contiguous()
     return one(x64, d64), one(x64.abs(), d64.abs())
+
+
+FP16_MIN_NORMAL = 2.0 ** -14
+
+
+def nominal16(v, dtype):
+    """|v| as the MFMA's alignment sees a 16-bit operand (module docstring): fp16 values below the smallest normal
+    number, zero included, count as 2**-14."""
+    a = v.to(torch.float64).abs()
+    return a.clamp_min(FP16_MIN_NORMAL) if dtype == torch.float16 else a
+
+
+def conv_wgrad_nominal_mag(x, dy, R, S, stride, pad, dtype):
+    """``conv_wgrad_ref``'s mag [K, R, S, C] over the nominal operand magnitudes (``nominal16``; the zero padding of an
+    fp16 image counts as 2**-14): equal to the plain mag where every operand is a normal number."""
+    N, H, W, C = x.shape
+    _, P, Q, K = dy.shape
+    fill = FP16_MIN_NORMAL if dtype == torch.float16 else 0.0
+    xn = F.pad(nominal16(x, dtype).permute(0, 3, 1, 2), (pad, pad, pad, pad), value=fill)
+    cols = F.unfold(xn, (R, S), padding=0, stride=stride)
+    dw = torch.matmul(cols, nominal16(dy, dtype).reshape(N, P * Q, K)).sum(0)
+    return dw.view(C, R, S, K).permute(3, 1, 2, 0).contiguous()
 
 
 def conv_int_operands(shape, values, seed):

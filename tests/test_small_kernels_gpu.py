@@ -64,23 +64,18 @@ def _run_xent(logits, ld, bias, tgt, B, ncls, dtype, loss_scale, grad_div, outpu
         C_.xent32(logits, ld, bias, tgt, B, ncls, out, d, ls, float(grad_div), rl, rc)
     else:
         C_.xent(logits, ld, bias, tgt, B, ncls, out, d, ls, float(grad_div), rl, rc)
-    l64 = logits[:, :ncls].double()
-    b64 = bias.double() if bias is not None else torch.zeros(ncls, dtype=torch.float64, device=DEV)
-    v64 = l64 + b64
-    loss = F.cross_entropy(v64, tgt, reduction="none")
-    bound = 2.0 ** -18 * (1 + v64.abs().max(1).values + loss.abs())
+    gs = (loss_scale if loss_scale is not None else 1.0) / grad_div
+    r = nm.xent_ref(logits, bias, tgt, ncls, gs, dtype)  # shared with the step audit (tests/_step_audit.py)
+    v64, loss, bound = r["v"], r["loss"], r["loss_bound"]
     nm.assert_within(rl, loss, bound, f"{name}: row loss", family="3 xent")
     # the bound is reachable: torch's fp32 cross entropy of the same values stays inside it
     nm.assert_within(F.cross_entropy(v64.float(), tgt, reduction="none"), loss, bound, f"{name}: torch fp32 loss")
     v32 = logits[:, :ncls].float() + (bias if bias is not None else 0.0)  # the fp32 values the kernel compares
     assert torch.equal(rc, (_first_argmax(v32) == tgt).float()), f"{name}: row_correct"
+    assert torch.equal(r["correct"], (_first_argmax(v32) == tgt).float())
     if outputs:
-        nm.assert_rounded(out, v64, l64.abs() + b64.abs(), torch.float32, k=1, name=f"{name}: out_logits", C=ncls,
-                          family="3 xent")
-        gs = (loss_scale if loss_scale is not None else 1.0) / grad_div
-        ref = (torch.softmax(v64, 1) - F.one_hot(tgt, ncls)) * gs
-        nm.assert_within(d[:, :ncls], ref, nm.half_ulp16(ref, dtype) + 2.0 ** -18 * gs, f"{name}: dlogits", ncls,
-                         family="3 xent")
+        nm.assert_rounded(out, v64, r["vmag"], torch.float32, k=1, name=f"{name}: out_logits", C=ncls, family="3 xent")
+        nm.assert_within(d[:, :ncls], r["dlogits"], r["dlogits_bound"], f"{name}: dlogits", ncls, family="3 xent")
         assert not bool(d[:, ncls:].float().ne(0).any()), f"{name}: dlogits padding columns must be zero"
     return rl, rc
 
