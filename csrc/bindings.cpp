@@ -32,6 +32,7 @@
 #include "kernels/loss.h"
 #include "kernels/optim.h"
 #include "kernels/pool.h"
+#include "kernels/pwconv.h"
 #include "kernels/stem.h"
 #include "kernels/vgg.h"
 
@@ -951,6 +952,63 @@ int64_t dwconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, i
   return p.splits;
 }
 
+// ------------------------------------------------------- pointwise (1x1) convolution (pwconv.hip)
+// 1x1, stride 1, pad 0, groups 1, no bias; x / y / dy / dx NHWC 16-bit seen as [M][channels], w [K][C] 16-bit
+// (the backward data takes w^T as a [C][K] tensor).  C % 8 == K % 8 == 0, 8 <= C, K <= 2048.
+bool pwconv_fits(int64_t M, int64_t C, int64_t K) { return pdt::pwconv_fits(M, C, K); }
+
+int pw_geom(const char* op, const Tensor& a, int64_t an, const Tensor& b, int64_t bn, const Tensor* w, int64_t M,
+            int64_t C, int64_t K) {
+  const int dt = dt16(a, op);
+  TORCH_CHECK(dt16(b, op) == dt && (w == nullptr || dt16(*w, op) == dt), op, ": mixed dtypes");
+  TORCH_CHECK(pdt::pwconv_fits(M, C, K), op, ": needs C % 8 == K % 8 == 0, 8 <= C, K <= 2048 and 1 <= M <= 2^30, got M = ",
+              M, ", C = ", C, ", K = ", K);
+  TORCH_CHECK(a.numel() == M * an && b.numel() == M * bn, op, ": operands hold ", a.numel(), " and ", b.numel(),
+              " elements, geometry needs ", M * an, " and ", M * bn);
+  TORCH_CHECK(w == nullptr || w->numel() == K * C, op, ": the weight must hold K * C = ", K * C, " elements");
+  for (const Tensor* t : {&a, &b, w})
+    TORCH_CHECK(t == nullptr || reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, op,
+                ": operands must be 16-byte aligned");
+  return dt;
+}
+
+// y[M][K] = x[M][C] * w[K][C]^T
+void pwconv_fwd(const Tensor& x, const Tensor& w, Tensor& y, int64_t M, int64_t C, int64_t K) {
+  const int dt = pw_geom("pwconv_fwd", x, C, y, K, &w, M, C, K);
+  pdt::pwconv_gemm_launch(dt, p16(x, "x"), p16(w, "w"), p16(y, "y"), M, (int)C, (int)K, false, cur_stream());
+  launched("pwconv_fwd");
+}
+
+// dx[M][C] = dy[M][K] * wt[C][K]^T   (wt = w^T, contiguous)
+void pwconv_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, int64_t M, int64_t C, int64_t K) {
+  const int dt = pw_geom("pwconv_dgrad", dx, C, dy, K, &wt, M, C, K);
+  pdt::pwconv_gemm_launch(dt, p16(dy, "dy"), p16(wt, "wt"), p16(dx, "dx"), M, (int)K, (int)C, true, cur_stream());
+  launched("pwconv_dgrad");
+}
+
+// (splits, pix_per_split, 64-wide C tiles, 64-wide K tiles): the caller allocates ws = [splits][K][C] fp32
+std::vector<int64_t> pwconv_wgrad_plan(int64_t M, int64_t C, int64_t K, int64_t target_blocks) {
+  TORCH_CHECK(pdt::pwconv_fits(M, C, K) && target_blocks >= 1 && target_blocks < (int64_t(1) << 30),
+              "pwconv_wgrad_plan: bad arguments");
+  const pdt::PwWgradPlan p = pdt::pwconv_wgrad_plan(M, (int)C, (int)K, (int)target_blocks);
+  return {p.splits, p.pix_per_split, p.c_tiles, p.k_tiles};
+}
+
+// partial slabs ws[splits][K][C] (fp32) of dw = dy^T * x for the plan of `target_blocks`; returns the split count to
+// pass to wgrad_reduce (rows = K, cols = C)
+int64_t pwconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t M, int64_t C, int64_t K,
+                     int64_t target_blocks) {
+  const int dt = pw_geom("pwconv_wgrad", x, C, dy, K, nullptr, M, C, K);
+  TORCH_CHECK(target_blocks >= 1 && target_blocks < (int64_t(1) << 30), "pwconv_wgrad: bad target_blocks");
+  const pdt::PwWgradPlan p = pdt::pwconv_wgrad_plan(M, (int)C, (int)K, (int)target_blocks);
+  TORCH_CHECK(ws.numel() >= (int64_t)p.splits * K * C, "pwconv_wgrad: ws holds ", ws.numel(), " floats, the plan needs ",
+              (int64_t)p.splits * K * C);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pf(ws, "ws")) % 16 == 0, "pwconv_wgrad: ws must be 16-byte aligned");
+  pdt::pwconv_wgrad_launch(dt, p16(x, "x"), p16(dy, "dy"), pf(ws, "ws"), M, (int)C, (int)K, p, cur_stream());
+  launched("pwconv_wgrad");
+  return p.splits;
+}
+
 // ------------------------------------------------------- fused BatchNorm + activation (bnact.hip)
 // x / g / out / dx: NHWC 16-bit viewed as [rows, C]; act: 0 identity, 1 ReLU, 2 ReLU6, 3 Hardswish.
 // The two reduce passes return (row blocks, row lanes per block): a thread's fp32 chain is
@@ -1644,6 +1702,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv_wgrad_plan", &dwconv_wgrad_plan, py::arg("npix"), py::arg("C"), py::arg("R"), py::arg("target_blocks"));
   m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("N"), py::arg("H"),
         py::arg("W"), py::arg("C"), py::arg("R"), py::arg("stride"), py::arg("target_blocks"));
+  m.def("pwconv_fits", &pwconv_fits, py::arg("M"), py::arg("C"), py::arg("K"));
+  m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("M"), py::arg("C"), py::arg("K"));
+  m.def("pwconv_dgrad", &pwconv_dgrad, py::arg("dy"), py::arg("wt"), py::arg("dx"), py::arg("M"), py::arg("C"),
+        py::arg("K"));
+  m.def("pwconv_wgrad_plan", &pwconv_wgrad_plan, py::arg("M"), py::arg("C"), py::arg("K"), py::arg("target_blocks"));
+  m.def("pwconv_wgrad", &pwconv_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("M"), py::arg("C"),
+        py::arg("K"), py::arg("target_blocks"));
   m.def("bn_relu_maxpool2", &bn_relu_maxpool2, py::arg("y"), py::arg("coef"), py::arg("out"), py::arg("idx"), py::arg("N"),
         py::arg("H"), py::arg("W"), py::arg("C"));
   m.def("maxpool2_bwd", &maxpool2_bwd);

@@ -165,6 +165,11 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
                         "where the training activations are 16-bit channels_last GPU tensors; elsewhere (CPU, fp32, "
                         "validation) the modules fall back to the stock ops; ignored when --sync_batchnorm converts "
                         "the model")
+    g.add_argument("--native-pointwise", default="off", choices=["off", "on"],
+                   help="torch engine: run qualifying 1x1 convs (stride 1, padding 0, groups 1, no bias, both channel "
+                        "counts % 8 == 0 and within 8..2048) on the native HIP pointwise kernels where the activations "
+                        "are 16-bit channels_last GPU tensors; elsewhere (CPU, fp32, validation) the modules fall back "
+                        "to F.conv2d")
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

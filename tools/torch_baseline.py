@@ -20,6 +20,8 @@ p.add_argument("--native-depthwise", default="off", choices=["off", "on"],
 p.add_argument("--native-bnact", default="off", choices=["off", "on"],
                help="on: qualifying BatchNorm2d (+ ReLU / ReLU6 / Hardswish) layers run on the native fused HIP kernels "
                     "(ops/bnact.py); off: MIOpen batch norm + a separate activation")
+p.add_argument("--native-pointwise", default="off", choices=["off", "on"],
+               help="on: qualifying 1x1 convs run on the native HIP kernels (ops/pointwise.py); off: MIOpen")
 a = p.parse_args()
 torch.backends.cudnn.benchmark = bool(a.benchmark)
 import threading
@@ -39,6 +41,11 @@ if a.native_depthwise == "on":
     from pytorch_distributed_template_amd.ops.depthwise import convert_depthwise
     n_dw = convert_depthwise(m)
     print(f"native depthwise: {n_dw} conv(s) converted", flush=True)
+n_pw = 0
+if a.native_pointwise == "on":
+    from pytorch_distributed_template_amd.ops.pointwise import convert_pointwise
+    n_pw = convert_pointwise(m)
+    print(f"native pointwise: {n_pw} conv(s) converted", flush=True)
 n_bn = n_act = 0
 if a.native_bnact == "on":
     from pytorch_distributed_template_amd.ops.bnact import convert_bnact
@@ -74,5 +81,6 @@ print()
 el = (time.time() - t) / a.steps
 print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl,
                   "native_depthwise": a.native_depthwise, "depthwise_converted": n_dw,
+                  "native_pointwise": a.native_pointwise, "pointwise_converted": n_pw,
                   "native_bnact": a.native_bnact, "bnact_converted": n_bn, "bnact_fused": n_act, "ms_per_step": el * 1e3,
                   "img_per_s": a.bs / el, "max_mem_GB": torch.cuda.max_memory_allocated() / 1e9}))
