@@ -33,6 +33,7 @@
 #include "kernels/optim.h"
 #include "kernels/pool.h"
 #include "kernels/pwconv.h"
+#include "kernels/stem3x3.h"
 #include "kernels/stem.h"
 #include "kernels/vgg.h"
 
@@ -1009,6 +1010,58 @@ int64_t pwconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t M, i
   return p.splits;
 }
 
+// ------------------------------------------------------- 3x3 / stride 2 / 3-channel first conv (stem3x3.hip)
+// x [N][H][W][3] fp32 NHWC (4-byte aligned), w [K][3][3][3] 16-bit KRSC, y / dy [N][P][Q][K] 16-bit, P = (H - 1) / 2 + 1,
+// Q = (W - 1) / 2 + 1; K % 8 == 0, 8 <= K <= 64.
+bool stem3x3_fits(int64_t N, int64_t H, int64_t W, int64_t K) { return pdt::stem3x3_fits(N, H, W, K); }
+
+// checks the image and the 16-bit [N][P][Q][K] operand against the geometry; returns that operand's dtype
+int stem_geom(const char* op, const Tensor& x, const Tensor& t16, int64_t N, int64_t H, int64_t W, int64_t K) {
+  const int dt = dt16(t16, op);
+  pf(x, "x");
+  TORCH_CHECK(pdt::stem3x3_fits(N, H, W, K), op, ": needs K % 8 == 0, 8 <= K <= 64, H, W >= 1, 1 <= N * P * Q <= 2^30 and "
+              "an image below 2^31 bytes, got N = ", N, ", H = ", H, ", W = ", W, ", K = ", K);
+  const int64_t M = N * pdt::stem3x3_out(H) * pdt::stem3x3_out(W);
+  TORCH_CHECK(x.numel() == N * H * W * 3 && t16.numel() == M * K, op, ": operands hold ", x.numel(), " and ",
+              t16.numel(), " elements, geometry needs ", N * H * W * 3, " and ", M * K);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t16.data_ptr()) % 16 == 0, op, ": the 16-bit operand must be 16-byte aligned");
+  return dt;
+}
+
+// y = conv3x3/2(x.to(dtype), w), rounded once
+void stem3x3_fwd(const Tensor& x, const Tensor& w, Tensor& y, int64_t N, int64_t H, int64_t W, int64_t K) {
+  const int dt = stem_geom("stem3x3_fwd", x, y, N, H, W, K);
+  TORCH_CHECK(dt16(w, "stem3x3_fwd") == dt, "stem3x3_fwd: mixed dtypes");
+  TORCH_CHECK(w.numel() == K * 27, "stem3x3_fwd: the weight must hold K * 27 = ", K * 27, " elements");
+  pdt::stem3x3_fwd_launch(dt, pf(x, "x"), p16(w, "w"), p16(y, "y"), N, (int)H, (int)W, (int)K, cur_stream());
+  launched("stem3x3_fwd");
+}
+
+// (splits, pix_per_split) for M = N * P * Q output pixels: the caller allocates ws = [splits][K][32] fp32
+std::vector<int64_t> stem3x3_wgrad_plan(int64_t M, int64_t K, int64_t target_blocks) {
+  TORCH_CHECK(M >= 1 && M <= pdt::kStemMaxPix && K >= pdt::kStemMinK && K <= pdt::kStemMaxK && K % 8 == 0 &&
+                  target_blocks >= 1 && target_blocks < (int64_t(1) << 30),
+              "stem3x3_wgrad_plan: bad arguments");
+  const pdt::StemWgradPlan p = pdt::stem3x3_wgrad_plan(M, (int)K, (int)target_blocks);
+  return {p.splits, p.pix_per_split};
+}
+
+// partial slabs ws[splits][K][32] (fp32) of dw[K][27] for the plan of `target_blocks`; returns the split count to pass
+// to wgrad_reduce (rows = K, cols = 27, ldw = 32, split_stride = K * 32)
+int64_t stem3x3_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, int64_t H, int64_t W, int64_t K,
+                      int64_t target_blocks) {
+  const int dt = stem_geom("stem3x3_wgrad", x, dy, N, H, W, K);
+  TORCH_CHECK(target_blocks >= 1 && target_blocks < (int64_t(1) << 30), "stem3x3_wgrad: bad target_blocks");
+  const int64_t M = N * pdt::stem3x3_out(H) * pdt::stem3x3_out(W);
+  const pdt::StemWgradPlan p = pdt::stem3x3_wgrad_plan(M, (int)K, (int)target_blocks);
+  TORCH_CHECK(ws.numel() >= (int64_t)p.splits * K * 32, "stem3x3_wgrad: ws holds ", ws.numel(),
+              " floats, the plan needs ", (int64_t)p.splits * K * 32);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pf(ws, "ws")) % 16 == 0, "stem3x3_wgrad: ws must be 16-byte aligned");
+  pdt::stem3x3_wgrad_launch(dt, pf(x, "x"), p16(dy, "dy"), pf(ws, "ws"), N, (int)H, (int)W, (int)K, p, cur_stream());
+  launched("stem3x3_wgrad");
+  return p.splits;
+}
+
 // ------------------------------------------------------- fused BatchNorm + activation (bnact.hip)
 // x / g / out / dx: NHWC 16-bit viewed as [rows, C]; act: 0 identity, 1 ReLU, 2 ReLU6, 3 Hardswish.
 // The two reduce passes return (row blocks, row lanes per block): a thread's fp32 chain is
@@ -1709,6 +1762,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pwconv_wgrad_plan", &pwconv_wgrad_plan, py::arg("M"), py::arg("C"), py::arg("K"), py::arg("target_blocks"));
   m.def("pwconv_wgrad", &pwconv_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("M"), py::arg("C"),
         py::arg("K"), py::arg("target_blocks"));
+  m.def("stem3x3_fits", &stem3x3_fits, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("K"));
+  m.def("stem3x3_fwd", &stem3x3_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("N"), py::arg("H"), py::arg("W"),
+        py::arg("K"));
+  m.def("stem3x3_wgrad_plan", &stem3x3_wgrad_plan, py::arg("M"), py::arg("K"), py::arg("target_blocks"));
+  m.def("stem3x3_wgrad", &stem3x3_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("K"), py::arg("target_blocks"));
   m.def("bn_relu_maxpool2", &bn_relu_maxpool2, py::arg("y"), py::arg("coef"), py::arg("out"), py::arg("idx"), py::arg("N"),
         py::arg("H"), py::arg("W"), py::arg("C"));
   m.def("maxpool2_bwd", &maxpool2_bwd);

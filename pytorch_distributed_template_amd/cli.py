@@ -170,6 +170,11 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
                         "counts % 8 == 0 and within 8..2048) on the native HIP pointwise kernels where the activations "
                         "are 16-bit channels_last GPU tensors; elsewhere (CPU, fp32, validation) the modules fall back "
                         "to F.conv2d")
+    g.add_argument("--native-stem", default="off", choices=["off", "on"],
+                   help="torch engine: run a qualifying first conv (3 input channels, 3x3, stride 2, padding 1, no bias, "
+                        "output channels % 8 == 0 and within 8..64) on the native HIP stem kernels where the image is an "
+                        "fp32 channels_last GPU tensor under 16-bit autocast; elsewhere (CPU, fp32, validation) the "
+                        "module falls back to F.conv2d")
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

@@ -344,6 +344,9 @@ def main(mode: str, argv: Optional[list] = None) -> int:
         from ..ops.pointwise import convert_pointwise
         ddp_print("=> native pointwise: {} conv(s) of {} converted".format(convert_pointwise(model), args.arch),
                   logger, rank)
+    if getattr(args, "native_stem", "off") == "on" and engine == "torch":
+        from ..ops.stemconv import convert_stem
+        ddp_print("=> native stem: {} conv(s) of {} converted".format(convert_stem(model), args.arch), logger, rank)
     if getattr(args, "native_bnact", "off") == "on" and engine == "torch":
         if distributed and bool(getattr(args, "sync_batchnorm", False)):
             # the trainer's condition for SyncBatchNorm.convert_sync_batchnorm, which rebuilds every _BatchNorm

@@ -22,6 +22,8 @@ p.add_argument("--native-bnact", default="off", choices=["off", "on"],
                     "(ops/bnact.py); off: MIOpen batch norm + a separate activation")
 p.add_argument("--native-pointwise", default="off", choices=["off", "on"],
                help="on: qualifying 1x1 convs run on the native HIP kernels (ops/pointwise.py); off: MIOpen")
+p.add_argument("--native-stem", default="off", choices=["off", "on"],
+               help="on: a qualifying 3x3/2 first conv runs on the native HIP kernels (ops/stemconv.py); off: MIOpen")
 a = p.parse_args()
 torch.backends.cudnn.benchmark = bool(a.benchmark)
 import threading
@@ -46,6 +48,11 @@ if a.native_pointwise == "on":
     from pytorch_distributed_template_amd.ops.pointwise import convert_pointwise
     n_pw = convert_pointwise(m)
     print(f"native pointwise: {n_pw} conv(s) converted", flush=True)
+n_stem = 0
+if a.native_stem == "on":
+    from pytorch_distributed_template_amd.ops.stemconv import convert_stem
+    n_stem = convert_stem(m)
+    print(f"native stem: {n_stem} conv(s) converted", flush=True)
 n_bn = n_act = 0
 if a.native_bnact == "on":
     from pytorch_distributed_template_amd.ops.bnact import convert_bnact
@@ -82,5 +89,6 @@ el = (time.time() - t) / a.steps
 print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl,
                   "native_depthwise": a.native_depthwise, "depthwise_converted": n_dw,
                   "native_pointwise": a.native_pointwise, "pointwise_converted": n_pw,
+                  "native_stem": a.native_stem, "stem_converted": n_stem,
                   "native_bnact": a.native_bnact, "bnact_converted": n_bn, "bnact_fused": n_act, "ms_per_step": el * 1e3,
                   "img_per_s": a.bs / el, "max_mem_GB": torch.cuda.max_memory_allocated() / 1e9}))
