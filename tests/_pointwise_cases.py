@@ -6,6 +6,11 @@ A geometry is ``(N, H, W, C, K)``: NHWC input [N, H, W, C], weight [K, C]; as a 
 it is ``(N, H, W, C, K, 1, 1, 0)``, which is where operands come from; references and magnitudes are
 tests/_numerics.py's.  Both layers of that module apply: layer A (integers) must come out bit for bit, layer B (reals)
 within ``assert_conv``'s bound with ``n`` the reduction length (C forward, K backward data, M = N*H*W weight gradient).
+
+A third layer, ``tiny``, exists for the weight gradient in fp16 only (``TINY_GEOMS``): dY is the ``real`` operand times
+2**-16, which is subnormal in fp16 (|dy| < 4) and nonzero unless |dy| < 2**-9 -- the unscaled fp16 gradients the torch
+engine hands the kernel.  The MFMA keeps such a sum to an ulp of the NOMINAL magnitudes (tests/_numerics.py): the layer
+is judged by ``assert_conv`` over ``conv_wgrad_nominal_mag``.
 """
 import torch
 
@@ -32,6 +37,8 @@ GEOMS = [
 WGRAD_PLAN_GEOM = (4, 28, 28, 32, 192)
 ISOLATION_GEOMS = [(2, 6, 6, 24, 144), (5, 13, 13, 40, 200)]
 WGRAD_TARGETS = [None, 1, 4096]  # None: the op's default
+TINY_GEOMS = [(3, 9, 11, 16, 96), (1, 3, 5, 144, 32)]  # the two smallest with a ragged reduction
+TINY_SCALE = 2.0 ** -16
 
 
 def conv_geom(g):
@@ -50,7 +57,7 @@ def case(kind, g, dtype, layer):
     """Operands (CPU, in ``dtype``) and the fp64 reference of one pass of one geometry, made once and shared
     (read-only) by every test: dict with the operands, ``ref``, ``mag`` and ``n`` (the reduction length).
     kind "fwd": x [N, H, W, C], w [K, C], ref [N, H, W, K]; "dgrad": dy [N, H, W, K], w [K, C], ref [N, H, W, C];
-    "wgrad": x, dy, ref [K, C]."""
+    "wgrad": x, dy, ref [K, C] (layer "tiny": module docstring; ``mag`` is then the nominal one)."""
     key = (kind, g, dtype, layer)
     if key in _cache:
         return _cache[key]
@@ -65,8 +72,13 @@ def case(kind, g, dtype, layer):
         ref, mag = nm.conv_dgrad_ref(dy, w, H, W, 1, 0)
         d = dict(dy=dy, w=w.reshape(K, C), ref=ref, mag=mag, n=K)
     else:
-        x, dy = cc.wgrad_operands(cg, dtype, layer)
+        x, dy = cc.wgrad_operands(cg, dtype, "real" if layer == "tiny" else layer)
+        if layer == "tiny":
+            assert dtype == torch.float16, "the tiny layer is fp16 only"
+            dy = (dy.float() * TINY_SCALE).to(dtype)
         ref, mag = nm.conv_wgrad_ref(x, dy, 1, 1, 1, 0)
+        if layer == "tiny":
+            mag = nm.conv_wgrad_nominal_mag(x, dy, 1, 1, 1, 0, dtype)
         d = dict(x=x, dy=dy, ref=ref.reshape(K, C), mag=mag.reshape(K, C), n=rows(g))
     _cache[key] = d
     return d

@@ -12,6 +12,11 @@ operands come from; references and magnitudes are tests/_numerics.py's.  Three l
 * ``round`` the in-kernel rounding: a plain fp32 ``randn`` image that is NOT representable in 16 bits, judged by the
   same bound against the reference of ``x.to(dtype)`` (round to nearest even), the value the kernel must form.
 
+* ``tiny``  weight gradient, fp16 only (``TINY_GEOMS``): dY is the ``real`` operand times 2**-16, which is subnormal in
+  fp16 (|dy| < 4) and nonzero unless |dy| < 2**-9 -- the unscaled fp16 gradients the torch engine hands the kernel.  The
+  MFMA keeps such a sum to an ulp of the NOMINAL magnitudes (tests/_numerics.py): judged by ``assert_conv`` over
+  ``conv_wgrad_nominal_mag``.
+
 The kernel is always handed an fp32 image: ``d["x32"]``.
 """
 import torch
@@ -39,6 +44,8 @@ WGRAD_PLAN_GEOM = (4, 56, 56, 32)
 ISOLATION_GEOMS = [(2, 9, 7, 24), (5, 17, 15, 48)]
 WGRAD_TARGETS = [None, 1, 4096]  # None: the op's default
 RED, RED_PAD = 27, 32            # the reduction and its MFMA K-step
+TINY_GEOMS = [(2, 9, 7, 24), (3, 10, 13, 32)]
+TINY_SCALE = 2.0 ** -16
 
 
 def conv_geom(g):
@@ -72,7 +79,7 @@ def case(kind, g, dtype, layer):
     if key in _cache:
         return _cache[key]
     cg = conv_geom(g)
-    src = "real" if layer == "round" else layer
+    src = "real" if layer in ("round", "tiny") else layer
     if kind == "fwd":
         x, w, _ = cc.fwd_operands(cg, dtype, src)
         x32 = _round_image(g, 101) if layer == "round" else x.float()
@@ -83,7 +90,12 @@ def case(kind, g, dtype, layer):
         x, dy = cc.wgrad_operands(cg, dtype, src)
         x32 = _round_image(g, 102) if layer == "round" else x.float()
         x = x32.to(dtype)
+        if layer == "tiny":
+            assert dtype == torch.float16, "the tiny layer is fp16 only"
+            dy = (dy.float() * TINY_SCALE).to(dtype)
         ref, mag = nm.conv_wgrad_ref(x, dy, 3, 3, 2, 1)
+        if layer == "tiny":
+            mag = nm.conv_wgrad_nominal_mag(x, dy, 3, 3, 2, 1, dtype)
         d = dict(x32=x32, x=x, dy=dy, ref=ref, mag=mag, n=rows(g))
     _cache[key] = d
     return d

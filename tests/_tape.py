@@ -1,9 +1,12 @@
 """Recording proxy for the native extension module (a plain module, not a conftest).
 
-``ex.C = Tape(ex.C)`` makes every kernel launch of a ResNetExecutor step leave an entry
-``Call(index, name, args, kwargs, outs)`` on ``tape.calls``: ``outs`` maps the argument position (or keyword name) of
-every tensor the launcher WRITES to a clone taken right after the call (the device is synchronised first, so with the
-executor on one stream -- PDT_WGRAD_STREAM=0 -- the clone holds what the kernel wrote).  The arguments themselves are
+``ex.C = Tape(ex.C)`` makes every kernel launch of a ResNetExecutor step (and ``monkeypatch.setattr(native, "C",
+Tape(native.C))`` every launch of the torch engine's converted modules, which read ``native.C.<name>`` at call time:
+tests/_torch_audit.py) leave an entry
+``Call(index, name, args, kwargs, outs, ret)`` on ``tape.calls``: ``outs`` maps the argument position (or keyword name)
+of every tensor the launcher WRITES to a clone taken right after the call (the device is synchronised first, so with the
+executor on one stream -- PDT_WGRAD_STREAM=0 -- the clone holds what the kernel wrote); ``ret`` is what the launcher
+returned (the ``(blocks, lanes)`` of the reduce passes, the splits of a weight gradient).  The arguments themselves are
 kept by reference: ``value_at`` resolves what an input tensor held at the time of a call from the latest earlier write
 to the same address, or, where the step never wrote it through the tape, from the live tensor.
 
@@ -15,7 +18,7 @@ from collections import namedtuple
 
 import torch
 
-Call = namedtuple("Call", "index name args kwargs outs")
+Call = namedtuple("Call", "index name args kwargs outs ret")
 
 # launcher -> positions (or keyword names) of the tensors it writes (csrc/bindings.cpp signatures)
 WRITES = {
@@ -44,9 +47,15 @@ WRITES = {
     "gconv_dgrad": (2, "bn_slots"),
     "stem_pool_bwd_reduce_out": (3,),
     "stem_pool_bwd_apply": (5,),
+    # the torch engine's converted modules (ops/bnact.py, depthwise.py, pointwise.py, stemconv.py)
+    "bnact_stats": (1,), "bnact_fwd": (2,), "bnact_bwd_reduce": (3,), "bnact_bwd_apply": (4,),  # slots, out, slots, dx
+    "dwconv_fwd": (2,), "dwconv_dgrad": (2,), "dwconv_wgrad": (2,),                             # y, dx, ws
+    "pwconv_fwd": (2,), "pwconv_dgrad": (2,), "pwconv_wgrad": (2,),
+    "stem3x3_fwd": (2,), "stem3x3_wgrad": (2,),
+    "sgd": (),                                # TorchTrainer's optimizer update goes through native.C too: not audited
 }
 
-_QUERY_SUFFIX = ("_supported", "_plan", "_blocks", "_mode")
+_QUERY_SUFFIX = ("_supported", "_plan", "_blocks", "_mode", "_fits")
 _QUERIES = {"stat_slots", "conv_dgrad_persistent", "dispatch_counts", "reset_dispatch_counts", "wgrad_blocks_3x3c64",
             "conv_m_tiles", "gconv_slice"}
 
@@ -83,7 +92,7 @@ class Tape:
                 if torch.is_tensor(t):
                     _sync(t)
                     outs[k] = t.detach().clone()
-            self.calls.append(Call(len(self.calls), name, args, kwargs, outs))
+            self.calls.append(Call(len(self.calls), name, args, kwargs, outs, ret))
             return ret
         recorded.__name__ = name
         return recorded

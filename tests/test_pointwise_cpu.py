@@ -144,6 +144,31 @@ def test_wgrad_missing_split_fails(g, dtype, layer):
         pc.judge_dw(pc.emul_wgrad(d["x"], d["dy"], 128, drop_last_split=True), d, layer, "missing split", None)
 
 
+@pytest.mark.parametrize("g", pc.TINY_GEOMS, ids=_ids)
+def test_tiny_layer_emulation_passes_and_mutations_fail(g):
+    """fp16 weight gradient with subnormal dY (the ``real`` operand times 2**-16), judged over the nominal magnitudes: the
+    emulation stays inside the bound; a missing split, a dropped pixel and gradient rows shifted by one output channel
+    leave it."""
+    dt = torch.float16
+    N, H, W, C, K = g
+    d = pc.case("wgrad", g, dt, "tiny")
+    a = d["dy"].float().abs()
+    # subnormal and nonzero: all but the |dy| >= 4 and the |dy| < 2**-9 of a normal sample
+    assert float((a < nm.FP16_MIN_NORMAL).float().mean()) > 0.999 and float((a > 0).float().mean()) > 0.99
+    assert torch.equal(d["x"], pc.case("wgrad", g, dt, "real")["x"])
+    plain = nm.conv_wgrad_ref(d["x"], d["dy"], 1, 1, 1, 0)[1].reshape(K, C)
+    assert bool((d["mag"] >= plain).all()) and bool((d["mag"] > plain).any())
+    for pps in (128, 1 << 20):
+        pc.judge_dw(pc.emul_wgrad(d["x"], d["dy"], pps), d, "tiny", f"tiny wgrad {g}", None)
+    good = pc.emul_wgrad(d["x"], d["dy"], 128)
+    cut = d["dy"].clone()
+    cut.view(-1, K)[-1] = 0
+    for name, bad in (("missing split", pc.emul_wgrad(d["x"], d["dy"], 128, drop_last_split=True)),
+                      ("dropped pixel", pc.emul_wgrad(d["x"], cut, 128)), ("rows shifted by one", good.roll(1, 0))):
+        with pytest.raises(AssertionError):
+            pc.judge_dw(bad, d, "tiny", name, None)
+
+
 # ------------------------------------------------------------------------------ module conversion
 @pytest.mark.parametrize("arch,count", COUNTS)
 def test_convert_counts(arch, count):

@@ -99,6 +99,21 @@ def test_pwconv_wgrad(g, dtype, layer):
         assert s1 == 1 and s2 > 8
 
 
+@pytest.mark.parametrize("g", pc.TINY_GEOMS, ids=_ids)
+def test_pwconv_wgrad_subnormal_dy(g):
+    """fp16 dY that is subnormal (what the unscaled fp16 torch-engine step hands the kernel): within ``assert_conv``'s bound
+    over the nominal magnitudes (tests/_numerics.py), for every split count, bit for bit the same on a second run."""
+    pw = _pw()
+    d = pc.case("wgrad", g, torch.float16, "tiny")
+    x, dy = d["x"].to(DEV), d["dy"].to(DEV)
+    assert float((dy.float().abs() < 2.0 ** -14).float().mean()) > 0.999 and float((dy != 0).float().mean()) > 0.99
+    for tb in pc.WGRAD_TARGETS:
+        kw = {} if tb is None else {"target_blocks": tb}
+        dw = pw.pwconv_wgrad(x, dy, **kw)
+        pc.judge_dw(dw.cpu(), d, "tiny", f"tiny wgrad {g} target_blocks={tb}", "pwconv_wgrad_tiny")
+        assert torch.equal(dw, pw.pwconv_wgrad(x, dy, **kw))
+
+
 def test_plan_and_size_predicate():
     """The plan covers every pixel with whole reduction steps, and the size predicate is the contract."""
     C_ = _C()

@@ -132,6 +132,26 @@ def test_truncated_image_fails_a_weight_gradient(dtype):
     assert rejected
 
 
+@pytest.mark.parametrize("g", sc.TINY_GEOMS, ids=_ids)
+def test_tiny_layer_emulation_passes_and_mutations_fail(g):
+    """fp16 weight gradient with subnormal dY (the ``real`` operand times 2**-16), judged over the nominal magnitudes: the
+    emulation stays inside the bound; a missing split, a dropped centre tap and R / S swapped leave it."""
+    dt = torch.float16
+    d = sc.case("wgrad", g, dt, "tiny")
+    a = d["dy"].float().abs()
+    # subnormal and nonzero: all but the |dy| >= 4 and the |dy| < 2**-9 of a normal sample
+    assert float((a < nm.FP16_MIN_NORMAL).float().mean()) > 0.999 and float((a > 0).float().mean()) > 0.99
+    assert torch.equal(d["x32"], sc.case("wgrad", g, dt, "real")["x32"])
+    plain = nm.conv_wgrad_ref(d["x"], d["dy"], 3, 3, 2, 1)[1]
+    assert bool((d["mag"] >= plain).all()) and bool((d["mag"] > plain).any())
+    for pps in (32, 1 << 20):
+        sc.judge_dw(sc.emul_wgrad(d["x32"], d["dy"], dt, pps), d, "tiny", f"tiny wgrad {g}", None)
+    for name, mut in (("missing split", dict(drop_last_split=True)), ("dropped tap", dict(drop_tap=(1, 1))),
+                      ("R and S swapped", dict(swap_rs=True))):
+        with pytest.raises(AssertionError):
+            sc.judge_dw(sc.emul_wgrad(d["x32"], d["dy"], dt, 32, **mut), d, "tiny", name, None)
+
+
 @pytest.mark.parametrize("layer", sc.LAYERS)
 @pytest.mark.parametrize("g,dtype", GD, ids=_ids)
 def test_wgrad_missing_split_fails(g, dtype, layer):
