@@ -132,6 +132,11 @@ class VGGExecutor(ResNetExecutor):
     """Runs a torchvision-layout :class:`VGG` or :class:`AlexNet` on one GPU (same public interface as
     :class:`ResNetExecutor`)."""
 
+    # a step's dropout launches draw with seed + 0, seed + 1 and seed + 7 (offsets below 8); consecutive steps' seeds
+    # are this far apart, so that no two launches of any two steps share one (a stride of 1 gave the first hidden layer
+    # the keep mask the second one had in the step before)
+    _DROP_STRIDE = 16
+
     def __init__(self, model: nn.Module, flat, device: torch.device, dtype: torch.dtype,
                  grad_ready: Optional[Callable[[int], None]] = None, syncbn_group=None, wgrad_blocks: int = 2048,
                  wgrad_blocks_1x1: int = 512, autotune: bool = False,
@@ -465,7 +470,7 @@ class VGGExecutor(ResNetExecutor):
         Cn.nhwc_nchw16(x, featc, N, h * w, C_last, True)
         p = self.p_drop if train else 0.0
         self._drop_step += 1
-        seed = (self._drop_seed * 0x100000001B3 + self._drop_step) & 0x7FFFFFFFFFFFFFFF
+        seed = (self._drop_seed * 0x100000001B3 + self._DROP_STRIDE * self._drop_step) & 0x7FFFFFFFFFFFFFFF
         a_in = featc.view(N, self.feat)
         x0 = None
         if self.drop_first:  # AlexNet: Dropout on the (post-ReLU) features -> fc_act_fwd with a zero bias

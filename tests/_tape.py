@@ -1,6 +1,6 @@
 """Recording proxy for the native extension module (a plain module, not a conftest).
 
-``ex.C = Tape(ex.C)`` makes every kernel launch of a ResNetExecutor step (and ``monkeypatch.setattr(native, "C",
+``ex.C = Tape(ex.C)`` makes every kernel launch of a ResNetExecutor or VGGExecutor step (and ``monkeypatch.setattr(native, "C",
 Tape(native.C))`` every launch of the torch engine's converted modules, which read ``native.C.<name>`` at call time:
 tests/_torch_audit.py) leave an entry
 ``Call(index, name, args, kwargs, outs, ret)`` on ``tape.calls``: ``outs`` maps the argument position (or keyword name)
@@ -52,6 +52,14 @@ WRITES = {
     "dwconv_fwd": (2,), "dwconv_dgrad": (2,), "dwconv_wgrad": (2,),                             # y, dx, ws
     "pwconv_fwd": (2,), "pwconv_dgrad": (2,), "pwconv_wgrad": (2,),
     "stem3x3_fwd": (2,), "stem3x3_wgrad": (2,),
+    # the VGG / AlexNet executor (models/executor_vgg.py, csrc/kernels/vgg.hip); its classifier GEMMs are torch.mm(out=)
+    # outside the extension: tests/_vgg_audit.py takes those from ``saved`` and the executor's buffers
+    "bias_coef": (1,),
+    "bn_relu_maxpool2": (2, 3),               # pooled out, argmax (None in eval)
+    "maxpool2_bwd": (5,), "maxpool_bwd_relu": (4,),
+    "pooled_bwd_reduce": (3,),                # BN-backward slots
+    "fc_act_fwd": (2,), "fc_act_bwd": (2,),
+    "nhwc_nchw16": (1,),
     "sgd": (),                                # TorchTrainer's optimizer update goes through native.C too: not audited
 }
 
