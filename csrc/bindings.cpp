@@ -980,6 +980,19 @@ void pwconv_fwd(const Tensor& x, const Tensor& w, Tensor& y, int64_t M, int64_t 
   launched("pwconv_fwd");
 }
 
+// the same y, plus slots[kStatSlots][K][2] fp64 = (sum y, sum y^2) per channel of the rounded y (what bn_finalize_slots
+// reads); max_blocks: persistent blocks aimed for (0 = the forward's default).  Returns (partial rows, fp32 chain).
+std::vector<int64_t> pwconv_fwd_stats(const Tensor& x, const Tensor& w, Tensor& y, Tensor& slots, int64_t M, int64_t C,
+                                      int64_t K, int64_t max_blocks) {
+  const int dt = pw_geom("pwconv_fwd_stats", x, C, y, K, &w, M, C, K);
+  TORCH_CHECK(slots.numel() >= pdt::kStatSlots * K * 2, "pwconv_fwd_stats: slots too small");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks < (int64_t(1) << 30), "pwconv_fwd_stats: bad max_blocks");
+  const pdt::PwStatsPlan p = pdt::pwconv_fwd_stats_launch(dt, p16(x, "x"), p16(w, "w"), p16(y, "y"), pd(slots, "slots"),
+                                                          M, (int)C, (int)K, (int)max_blocks, cur_stream());
+  launched("pwconv_fwd_stats");
+  return {p.row_blocks, p.chain};
+}
+
 // dx[M][C] = dy[M][K] * wt[C][K]^T   (wt = w^T, contiguous)
 void pwconv_dgrad(const Tensor& dy, const Tensor& wt, Tensor& dx, int64_t M, int64_t C, int64_t K) {
   const int dt = pw_geom("pwconv_dgrad", dx, C, dy, K, &wt, M, C, K);
@@ -1757,6 +1770,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("W"), py::arg("C"), py::arg("R"), py::arg("stride"), py::arg("target_blocks"));
   m.def("pwconv_fits", &pwconv_fits, py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("M"), py::arg("C"), py::arg("K"));
+  m.def("pwconv_fwd_stats", &pwconv_fwd_stats, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("slots"), py::arg("M"),
+        py::arg("C"), py::arg("K"), py::arg("max_blocks"));
   m.def("pwconv_dgrad", &pwconv_dgrad, py::arg("dy"), py::arg("wt"), py::arg("dx"), py::arg("M"), py::arg("C"),
         py::arg("K"));
   m.def("pwconv_wgrad_plan", &pwconv_wgrad_plan, py::arg("M"), py::arg("C"), py::arg("K"), py::arg("target_blocks"));

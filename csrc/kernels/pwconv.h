@@ -19,6 +19,18 @@ inline bool pwconv_fits(int64_t M, int64_t C, int64_t K) {
 void pwconv_gemm_launch(int dtype, const uint16_t* in, const uint16_t* B, uint16_t* out, int64_t M, int R, int N,
                         bool dgrad, hipStream_t s);
 
+// The forward with the BatchNorm statistics of its own (rounded) output: y as pwconv_gemm_launch writes it, bit for bit,
+// and slots[kStatSlots][K][2] fp64 (sum y, sum y^2 per channel), the layout bn_finalize_slots reads.  The GEMM blocks
+// emit fp32 partial rows [row_blocks][K][2] (stream-ordered scratch) that stat_rows_reduce folds; no atomics.
+// max_blocks: the persistent blocks the launch aims for (0 = the forward's own 1536); fewer make a block walk more
+// tiles.  chain: the longest run of fp32 additions a statistic passes through before the fp64 sums.
+struct PwStatsPlan {
+  int row_blocks;  // partial rows = persistent blocks per output slice
+  int chain;
+};
+PwStatsPlan pwconv_fwd_stats_launch(int dtype, const uint16_t* x, const uint16_t* w, uint16_t* y, double* slots,
+                                    int64_t M, int C, int K, int max_blocks, hipStream_t s);
+
 struct PwWgradPlan {
   int splits;         // partial slabs
   int pix_per_split;  // pixels per slab: a multiple of the 128-pixel reduction step

@@ -21,6 +21,7 @@
 //     wave taking 32 pixels of a step; the waves are summed through LDS in a fixed order and the block writes one
 //     fp32 partial tile of its split's slab [split][K][C] for wgrad_reduce (no atomics: bit-identical runs).
 #include "../common.h"
+#include "conv_fwd.h"
 #include "pwconv.h"
 
 namespace pdt {
@@ -43,11 +44,30 @@ PDT_DEVICE uint32_t pw_off(uint32_t a, uint32_t b) { return ((a | b) & kOOB) ? k
 // lane (rows 4 * fq + r) the 8 consecutive channels p * 32 + 8 * fq + [0, 8)
 PDT_DEVICE int pw_frag_ch(int i, int row) { return (i >> 1) * 32 + (row >> 2) * 8 + (i & 1) * 4 + (row & 3); }
 
-template <int DT, int NG, int PT, int KS>
+// Sum over the 16 lanes of a DPP row in a fixed butterfly (lane ^ 1, lane ^ 2, the half's mirror, the row's mirror):
+// every lane of the row ends with the same total.  Pure VALU.
+template <int CTRL>
+PDT_DEVICE float pw_dpp(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+}
+PDT_DEVICE float pw_row16_fold(float v) {
+  v += pw_dpp<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  v += pw_dpp<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  v += pw_dpp<0x141>(v);  // row_half_mirror
+  v += pw_dpp<0x140>(v);  // row_mirror
+  return v;
+}
+
+// STATS: the block also emits the BatchNorm statistics (sum y, sum y^2 per channel, of the ROUNDED outputs) of the
+// rows it wrote, as its slice of one fp32 partial row srows[blockIdx.x / nslices][N][2] (col_reduce.h's [C][K = 2]
+// layout) for stat_rows_reduce.  A lane keeps the sums of its 8 * NG channels across every tile the block walks
+// (rows past M and channels past N come from zero-filled operands: their outputs are exactly 0 and add nothing),
+// the 16 lanes that share the channels are folded by DPP, the 4 waves through LDS in wave order.  No atomics.
+template <int DT, int NG, int PT, int KS, bool STATS>
 __global__ __launch_bounds__(256) void pwconv_gemm_kernel(const uint16_t* __restrict__ in,
                                                           const uint16_t* __restrict__ B,
                                                           uint16_t* __restrict__ out, int64_t M, int R, int N,
-                                                          int nslices, int mtiles) {
+                                                          int nslices, int mtiles, float* __restrict__ srows) {
   using E = E16<DT>;
   typedef typename E::vec8 vec8;
   constexpr int NF = NG * 2;   // 16-channel weight fragments of the slice
@@ -85,6 +105,14 @@ __global__ __launch_bounds__(256) void pwconv_gemm_kernel(const uint16_t* __rest
 #pragma unroll
       for (int kk = 0; kk < KS; ++kk)
         ares[i][kk] = __builtin_bit_cast(vec8, pw_load16(rb, gok[i >> 1] ? pw_off(wrow[i], kpart(kk)) : kOOB));
+  }
+
+  float st[STATS ? NG : 1][2][8];  // [group][sum, sum of squares][channel of the lane's 8]
+  if constexpr (STATS) {
+#pragma unroll
+    for (int p = 0; p < NG; ++p)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) st[p][0][e] = st[p][1][e] = 0.f;
   }
 
   for (int t = blockIdx.x / nslices; t < mtiles; t += tstride) {
@@ -163,7 +191,39 @@ __global__ __launch_bounds__(256) void pwconv_gemm_kernel(const uint16_t* __rest
         pk.w = E::pack2(acc[2 * p + 1][j][2], acc[2 * p + 1][j][3]);
         const uint32_t off = (row < rows && ch < N) ? ((uint32_t)row * (uint32_t)N + (uint32_t)ch) * 2u : kOOB;
         pw_store16(ro, off, pk);
+        if constexpr (STATS) {
+          uint16_t h[8];
+          unpack8(pk, h);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float f = E::to_f(h[e]);
+            st[p][0][e] += f;
+            st[p][1][e] = fmaf(f, f, st[p][1][e]);  // the square of a 16-bit value is exact in fp32
+          }
+        }
       }
+    }
+  }
+
+  if constexpr (STATS) {
+    __shared__ float red[4][NG * 32][2];
+#pragma unroll
+    for (int p = 0; p < NG; ++p)
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float t = pw_row16_fold(st[p][k][e]);
+          if (fr == 0) red[wave][p * 32 + 8 * fq + e][k] = t;
+        }
+    __syncthreads();
+    const int idx = threadIdx.x;  // (channel of the slice, quantity)
+    if (idx < NG * 64 && n0 + (idx >> 1) < N) {
+      const float* r0 = &red[0][0][0];
+      float t = r0[idx];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) t += r0[w * NG * 64 + idx];
+      srows[((int64_t)(blockIdx.x / nslices) * N + n0) * 2 + idx] = t;
     }
   }
 }
@@ -290,29 +350,40 @@ __global__ __launch_bounds__(256) void pwconv_wgrad_kernel(const uint16_t* __res
 // persistent blocks the GEMM aims for: a few per CU (256 CUs)
 constexpr int kPwGemmBlocks = 1536;
 
-template <int DT, int NG, int PT>
-void pw_gemm_go(const uint16_t* in, const uint16_t* B, uint16_t* out, int64_t M, int R, int N, hipStream_t s) {
+// STATS: the statistics kernels; their partial rows live in stream-ordered scratch and are folded into the fp64
+// `slots` right behind the GEMM.  Returns (row blocks per slice, longest fp32 chain of a statistic).
+template <int DT, int NG, int PT, bool STATS>
+PwStatsPlan pw_gemm_go(const uint16_t* in, const uint16_t* B, uint16_t* out, int64_t M, int R, int N, double* slots,
+                       int max_blocks, hipStream_t s) {
   const int nslices = (N + NG * 32 - 1) / (NG * 32);
   const int64_t BR = 4 * PT * 16;
   const int mtiles = (int)((M + BR - 1) / BR);
-  int per = kPwGemmBlocks / nslices;
+  int per = max_blocks / nslices;
   if (per < 1) per = 1;
   if (per > mtiles) per = mtiles;
   const dim3 g((unsigned)(per * nslices));
-#define PDT_PW_G(KS) \
-  hipLaunchKernelGGL((pwconv_gemm_kernel<DT, NG, PT, KS>), g, dim3(256), 0, s, in, B, out, M, R, N, nslices, mtiles)
+  // every block owns at least one tile (per <= mtiles) and writes its slice of its partial row exactly once
+  Scratch part(STATS ? (size_t)per * N * 2 * sizeof(float) : 0, s);
+  float* srows = part.as<float>();
+#define PDT_PW_G(KS)                                                                                                 \
+  hipLaunchKernelGGL((pwconv_gemm_kernel<DT, NG, PT, KS, STATS>), g, dim3(256), 0, s, in, B, out, M, R, N, nslices, \
+                     mtiles, srows)
   if (R <= 32) PDT_PW_G(1);
   else if (R <= 64) PDT_PW_G(2);
   else PDT_PW_G(0);
 #undef PDT_PW_G
+  if constexpr (STATS) stat_rows_reduce_launch(srows, per, N * 2, slots, s);
+  // the lane's chain over its tiles (PT rows each), the 16-lane fold, the 4-wave fold
+  return PwStatsPlan{per, (mtiles + per - 1) / per * PT + 16 + 4};
 }
 
-template <int DT>
-void pw_gemm_dt(const uint16_t* in, const uint16_t* B, uint16_t* out, int64_t M, int R, int N, hipStream_t s) {
+template <int DT, bool STATS>
+PwStatsPlan pw_gemm_dt(const uint16_t* in, const uint16_t* B, uint16_t* out, int64_t M, int R, int N, double* slots,
+                       int max_blocks, hipStream_t s) {
   // the slice width follows the output width alone: no per-shape table
-  if (N <= 32) pw_gemm_go<DT, 1, 4>(in, B, out, M, R, N, s);
-  else if (N <= 64) pw_gemm_go<DT, 2, 4>(in, B, out, M, R, N, s);
-  else pw_gemm_go<DT, 4, 2>(in, B, out, M, R, N, s);
+  if (N <= 32) return pw_gemm_go<DT, 1, 4, STATS>(in, B, out, M, R, N, slots, max_blocks, s);
+  if (N <= 64) return pw_gemm_go<DT, 2, 4, STATS>(in, B, out, M, R, N, slots, max_blocks, s);
+  return pw_gemm_go<DT, 4, 2, STATS>(in, B, out, M, R, N, slots, max_blocks, s);
 }
 
 }  // namespace
@@ -322,8 +393,18 @@ void pwconv_gemm_launch(int dtype, const uint16_t* in, const uint16_t* B, uint16
   if (!pwconv_fits(M, R, N)) pdt_hip_fail("pwconv_gemm_launch: operand outside the kernels' addressing", hipErrorInvalidValue, __FILE__, __LINE__);
   if (dgrad) PDT_COUNT("pwconv_dgrad");
   else PDT_COUNT("pwconv_fwd");
-  if (dtype == kBF16) pw_gemm_dt<kBF16>(in, B, out, M, R, N, s);
-  else pw_gemm_dt<kF16>(in, B, out, M, R, N, s);
+  if (dtype == kBF16) pw_gemm_dt<kBF16, false>(in, B, out, M, R, N, nullptr, kPwGemmBlocks, s);
+  else pw_gemm_dt<kF16, false>(in, B, out, M, R, N, nullptr, kPwGemmBlocks, s);
+}
+
+PwStatsPlan pwconv_fwd_stats_launch(int dtype, const uint16_t* x, const uint16_t* w, uint16_t* y, double* slots,
+                                    int64_t M, int C, int K, int max_blocks, hipStream_t s) {
+  if (!pwconv_fits(M, C, K) || max_blocks < 0)
+    pdt_hip_fail("pwconv_fwd_stats_launch: operand outside the kernels' addressing", hipErrorInvalidValue, __FILE__, __LINE__);
+  PDT_COUNT("pwconv_fwd_stats");
+  if (max_blocks == 0) max_blocks = kPwGemmBlocks;
+  if (dtype == kBF16) return pw_gemm_dt<kBF16, true>(x, w, y, M, C, K, slots, max_blocks, s);
+  return pw_gemm_dt<kF16, true>(x, w, y, M, C, K, slots, max_blocks, s);
 }
 
 PwWgradPlan pwconv_wgrad_plan(int64_t M, int C, int K, int target_blocks) {

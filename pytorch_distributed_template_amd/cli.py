@@ -175,6 +175,11 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
                         "output channels % 8 == 0 and within 8..64) on the native HIP stem kernels where the image is an "
                         "fp32 channels_last GPU tensor under 16-bit autocast; elsewhere (CPU, fp32, validation) the "
                         "module falls back to F.conv2d")
+    g.add_argument("--native-convstats", default="off", choices=["off", "on"],
+                   help="torch engine, with --native-pointwise on and --native-bnact on: a converted 1x1 conv directly "
+                        "followed by its converted BatchNorm inside an nn.Sequential forms the BatchNorm statistics in "
+                        "its own epilogue, so the BatchNorm does not read the conv output again for them; ignored "
+                        "when either of the two conversions is off or ignored")
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

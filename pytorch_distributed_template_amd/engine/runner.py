@@ -357,6 +357,16 @@ def main(mode: str, argv: Optional[list] = None) -> int:
             n_bn, n_absorbed = convert_bnact(model)
             ddp_print("=> native bnact: {} BatchNorm(s) of {} converted, {} activation(s) fused".format(
                 n_bn, args.arch, n_absorbed), logger, rank)
+    if getattr(args, "native_convstats", "off") == "on" and engine == "torch":
+        # pairs of the two conversions above: it needs both
+        if getattr(args, "native_pointwise", "off") != "on" or getattr(args, "native_bnact", "off") != "on":
+            ddp_print("=> native convstats: ignored, it needs --native-pointwise on and --native-bnact on", logger, rank)
+        elif distributed and bool(getattr(args, "sync_batchnorm", False)):
+            ddp_print("=> native convstats: ignored, --sync_batchnorm converts the model's BatchNorms", logger, rank)
+        else:
+            from ..ops.convstats import convert_convstats
+            ddp_print("=> native convstats: {} conv/BatchNorm pair(s) of {} fused".format(
+                convert_convstats(model), args.arch), logger, rank)
     trainer = build_trainer(mode, model, args, device, dtype, engine, world)
     optimizer = trainer.optimizer
     gn = getattr(args, "gpu_normalize", "off")

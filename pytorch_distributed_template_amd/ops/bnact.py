@@ -43,8 +43,18 @@ def bnact_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, runnin
     rows = x.numel() // C
     slots = _slots(C, x.device)
     native.C.bnact_stats(x, slots, rows, C)
-    coef = torch.empty(4 * C, dtype=torch.float32, device=x.device)
-    sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+    return bnact_coef_from_slots(slots, rows, gamma, beta, running_mean, running_var, eps, momentum, update_running)
+
+
+def bnact_coef_from_slots(slots: torch.Tensor, rows: int, gamma: torch.Tensor, beta: torch.Tensor,
+                          running_mean: torch.Tensor, running_var: torch.Tensor, eps: float, momentum: float,
+                          update_running: bool = True) -> torch.Tensor:
+    """The finalize half of :func:`bnact_stats`: ``coef[4 * C]`` from fp64 ``slots[stat_slots, C, 2]`` of
+    ``(sum x, sum x**2)`` over ``rows`` values per channel, whoever filled them (``bnact_stats`` or the producing conv,
+    ``ops.pointwise.pwconv_fwd_stats``); updates the running statistics in place."""
+    C = gamma.numel()
+    coef = torch.empty(4 * C, dtype=torch.float32, device=slots.device)
+    sums = torch.empty(2 * C, dtype=torch.float64, device=slots.device)
     native.C.bn_finalize_slots(slots, float(rows), gamma, beta, eps, momentum, running_mean, running_var, coef, sums,
                                update_running)
     return coef
@@ -84,6 +94,16 @@ def bnact_bwd_apply(g: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, bcoef:
     return dx
 
 
+# The hand-over of a producing conv's statistics (ops.pointwise.PointwiseConv2d with ``emit_stats``): a plain Python
+# attribute ``(slots, version)`` on the very tensor object the conv returned, ``version`` being its ``_version`` then.
+CONV_STATS_ATTR = "_pdt_conv_stats"
+
+
+def take_conv_stats(t: torch.Tensor):
+    """Remove and return the ``(slots, version)`` a conv attached to ``t``, or ``None``."""
+    return t.__dict__.pop(CONV_STATS_ATTR, None)
+
+
 def qualifies(m: nn.BatchNorm2d) -> bool:
     """The BatchNorms the kernels cover (everything else stays on ``F.batch_norm``)."""
     return (m.affine and m.track_running_stats and m.momentum is not None and m.num_features % 8 == 0
@@ -95,9 +115,13 @@ class _BNActFn(torch.autograd.Function):
     per-channel coefficients only: the backward recomputes the pre-activation value from ``x``."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, act):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, act, slots=None):
         xh = x.permute(0, 2, 3, 1)  # NHWC view of the channels_last storage: no copy
-        coef = bnact_stats(xh, gamma.detach(), beta.detach(), running_mean, running_var, eps, momentum)
+        if slots is None:
+            coef = bnact_stats(xh, gamma.detach(), beta.detach(), running_mean, running_var, eps, momentum)
+        else:  # the statistics of x from the conv that produced it: a non-differentiable extra, same autograd
+            coef = bnact_coef_from_slots(slots, xh.numel() // xh.shape[-1], gamma.detach(), beta.detach(),
+                                         running_mean, running_var, eps, momentum)
         out = bnact_fwd(xh, coef, act)
         ctx.save_for_backward(x, coef, gamma)
         ctx.act = act
@@ -116,7 +140,7 @@ class _BNActFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = bnact_bwd_apply(g, xh, coef, bcoef, ctx.act).permute(0, 3, 1, 2)
-        return dx, dgamma, dbeta, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
 class BNAct2d(nn.BatchNorm2d):
@@ -138,14 +162,24 @@ class BNAct2d(nn.BatchNorm2d):
         return super().extra_repr() + f", act={self.act}"
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
+        handed = take_conv_stats(input)  # removed whatever path is taken below
         if (self.training and input.is_cuda and input.dtype in _DTYPES and input.dim() == 4 and qualifies(self)
                 and self.weight.dtype == torch.float32 and input.shape[1] == self.num_features
                 and input.numel() // self.num_features >= 2
                 and input.is_contiguous(memory_format=torch.channels_last)):
-            self.num_batches_tracked.add_(1)
-            return _BNActFn.apply(input, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
-                                  self.momentum, self.act)
+            return self._forward_native(input, handed)
         return _ACT_FN[self.act](super().forward(input))
+
+    def _forward_native(self, input: torch.Tensor, handed=None) -> torch.Tensor:
+        """The kernels' path.  ``handed``: the ``(slots, version)`` the producing conv attached to this very tensor; the
+        slots replace ``bnact_stats`` only if the tensor was not changed in place since and the width is this module's."""
+        self.num_batches_tracked.add_(1)
+        slots = None
+        if (handed is not None and handed[1] == input._version
+                and handed[0].numel() == native.C.stat_slots() * self.num_features * 2):
+            slots = handed[0]
+        return _BNActFn.apply(input, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
+                              self.momentum, self.act, slots)
 
 
 def _as_bnact(bn: nn.BatchNorm2d, act: str) -> BNAct2d:

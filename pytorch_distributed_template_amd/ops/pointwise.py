@@ -5,6 +5,7 @@ Functional ops (the unit-test surface, tests/test_pointwise_gpu.py) over NHWC 16
 ``C % 8 == K % 8 == 0`` and ``8 <= C, K <= 2048``:
 
 * :func:`pwconv_fwd`    forward, ``y = x @ w.T``
+* :func:`pwconv_fwd_stats`  the same forward plus the BatchNorm statistics (sum, sum of squares) of its rounded output
 * :func:`pwconv_dgrad`  gradient w.r.t. the input, ``dx = dy @ w`` (the same kernel on ``w.T``, transposed once here)
 * :func:`pwconv_wgrad`  gradient w.r.t. the weight, fp32, deterministic (per-split partial slabs + fixed-order sum)
 
@@ -20,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import native
+from .bnact import CONV_STATS_ATTR
 
 # blocks the weight gradient aims for: a few per CU (256 CUs, two 64 KiB-LDS blocks resident on each)
 WGRAD_TARGET_BLOCKS = 1024
@@ -39,6 +41,19 @@ def pwconv_fwd(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     y = torch.empty(x.shape[:-1] + (K,), dtype=x.dtype, device=x.device)
     native.C.pwconv_fwd(x, w, y, x.numel() // C, C, K)
     return y
+
+
+def pwconv_fwd_stats(x: torch.Tensor, w: torch.Tensor, max_blocks: int = 0):
+    """``(y, slots, (partial_rows, chain))``: ``y`` as :func:`pwconv_fwd` writes it, bit for bit, and the fp64
+    ``slots[stat_slots, K, 2]`` holding ``(sum y, sum y**2)`` per channel of the rounded ``y`` -- what
+    ``bn_finalize_slots`` (:func:`ops.bnact.bnact_coef_from_slots`) reads, so the BatchNorm behind the conv need not
+    read ``y`` again.  ``max_blocks``: persistent blocks the launch aims for (0: the forward's default); ``chain`` is the
+    longest run of fp32 additions a statistic passes through before the fp64 sums."""
+    K, C = w.shape
+    y = torch.empty(x.shape[:-1] + (K,), dtype=x.dtype, device=x.device)
+    slots = torch.empty(native.C.stat_slots() * K * 2, dtype=torch.float64, device=x.device)
+    rows, chain = native.C.pwconv_fwd_stats(x, w, y, slots, x.numel() // C, C, K, max_blocks)
+    return y, slots, (rows, chain)
 
 
 def pwconv_dgrad(dy: torch.Tensor, w: torch.Tensor, wt: torch.Tensor | None = None) -> torch.Tensor:
@@ -106,18 +121,50 @@ class _PointwiseFn(torch.autograd.Function):
         return dx, dw
 
 
+class _PointwiseStatsFn(torch.autograd.Function):
+    """:class:`_PointwiseFn` whose forward also returns the BatchNorm statistics slots of ``y`` (not differentiable:
+    the BatchNorm behind still differentiates through its statistics as a function of ``y``)."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        K, C = weight.shape[:2]
+        w16 = weight.detach().reshape(K, C).to(x.dtype)
+        y, slots, _ = pwconv_fwd_stats(x.permute(0, 2, 3, 1), w16)
+        ctx.save_for_backward(x, w16)
+        ctx.mark_non_differentiable(slots)
+        return y.permute(0, 3, 1, 2), slots
+
+    @staticmethod
+    def backward(ctx, gy, _gslots):
+        return _PointwiseFn.backward(ctx, gy)
+
+
 class PointwiseConv2d(nn.Conv2d):
     """``nn.Conv2d`` (same constructor, parameters and state-dict keys) that runs a qualifying 1x1 conv on the native
     kernels when its input is a 16-bit, dense ``channels_last`` GPU tensor within the kernels' addressing.  CPU, fp32,
-    NCHW inputs and non-qualifying configurations take ``F.conv2d`` exactly as the parent does."""
+    NCHW inputs and non-qualifying configurations take ``F.conv2d`` exactly as the parent does.
+
+    ``emit_stats`` (set by ``ops.convstats.convert_convstats`` when a ``BNAct2d`` directly follows): in training mode
+    the native path also forms the BatchNorm statistics of its output and hands them over as the attribute
+    ``ops.bnact.CONV_STATS_ATTR = (slots, version)`` of the tensor object it returns."""
+
+    emit_stats = False
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         if (input.is_cuda and input.dtype in _DTYPES and input.dim() == 4 and qualifies(self)
                 and input.is_contiguous(memory_format=torch.channels_last) and input.numel() > 0
                 and input.data_ptr() % 16 == 0  # the kernels' 16-byte accesses
                 and fits(input.numel() // self.in_channels, self.in_channels, self.out_channels)):
-            return _PointwiseFn.apply(input, self.weight)
+            return self._forward_native(input)
         return super().forward(input)
+
+    def _forward_native(self, input: torch.Tensor) -> torch.Tensor:
+        # a forward hook (added after the pairing) may return another tensor: the statistics would be wasted work
+        if self.emit_stats and self.training and not self._forward_hooks:
+            y, slots = _PointwiseStatsFn.apply(input, self.weight)
+            setattr(y, CONV_STATS_ATTR, (slots, y._version))
+            return y
+        return _PointwiseFn.apply(input, self.weight)
 
 
 def _as_pointwise(conv: nn.Conv2d) -> PointwiseConv2d:

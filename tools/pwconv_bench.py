@@ -10,7 +10,8 @@ with device events around windows of repeated calls after a warm-up, and reports
 arms, the bytes the pass has to move (forward: read x and w, write y; backward data: read dy and w, write dx; weight
 gradient: read x and dy, write dw), the native kernel's achieved TB/s and its share of the HBM streaming rate.
 ``--resources`` adds each pwconv kernel's VGPR / scratch / occupancy figures from the compile-time resource report
-(needs hipcc, no GPU).
+(needs hipcc, no GPU).  ``--stats`` times, per layer and the same way, the forward that also forms the BatchNorm
+statistics of its output (``pwconv_fwd_stats``) against ``pwconv_fwd`` followed by ``bnact_stats``.
 
 Not part of the framework: a measurement tool only.  Output: a markdown table on stdout, optionally ``--json FILE``.
 """
@@ -88,7 +89,8 @@ def demangle(sym):
     dt = "bf16" if a[0] == 0 else "fp16"
     if m.group(1) == "pwconv_gemm_kernel":
         ks = f"weights resident, {a[3]} K-step(s)" if a[3] else "K loop"
-        return f"gemm<{dt}, {a[1] * 32} ch x {a[2] * 64} rows, {ks}>"
+        stats = ", BN statistics" if len(a) > 4 and a[4] else ""
+        return f"gemm<{dt}, {a[1] * 32} ch x {a[2] * 64} rows, {ks}{stats}>"
     return f"wgrad<{dt}>"
 
 
@@ -126,6 +128,41 @@ def time_pair(fa, fb, min_time, rounds=3):
     return sorted(ta)[rounds // 2], sorted(tb)[rounds // 2]
 
 
+def stats_table(a, shapes, pw, dev, dt):
+    """--stats: per layer, the conv that also forms the statistics of the BatchNorm behind it against the conv followed
+    by the BatchNorm's own statistics pass (which reads the conv output again)."""
+    from pytorch_distributed_template_amd.ops import native
+    rows = []
+    print(f"## {a.arch} @ {a.image_size}, batch {a.bs}, {a.dtype}: pwconv_fwd_stats vs pwconv_fwd + bnact_stats\n")
+    print("| H_in | C -> K | layers | fused us | pwconv_fwd + bnact_stats us | fused/unfused | saved us x layers | y MB |")
+    print("|---|---|---|---|---|---|---|---|")
+    for H, W, C, K, n in shapes:
+        M = a.bs * H * W
+        x = torch.randn(a.bs, H, W, C, device=dev).to(dt)
+        w = (torch.randn(K, C, device=dev) * C ** -0.5).to(dt)
+        slots = torch.empty(native.C.stat_slots() * K * 2, dtype=torch.float64, device=dev)
+
+        def unfused():
+            y = pw.pwconv_fwd(x, w)
+            native.C.bnact_stats(y, slots, M, K)
+
+        tf, tu = time_pair(lambda: pw.pwconv_fwd_stats(x, w), unfused, a.min_time)
+        rows.append(dict(arch=a.arch, H=H, W=W, C=C, K=K, layers=n, bs=a.bs, dtype=a.dtype, fused_us=tf * 1e6,
+                         unfused_us=tu * 1e6))
+        print(f"| {H} | {C} -> {K} | {n} | {tf * 1e6:.1f} | {tu * 1e6:.1f} | {tf / tu:.2f} | {(tu - tf) * 1e6 * n:.0f} | "
+              f"{M * K * 2 / 1e6:.1f} |", flush=True)
+        del x
+        torch.cuda.empty_cache()
+    tot_f = sum(r["fused_us"] * r["layers"] for r in rows)
+    tot_u = sum(r["unfused_us"] * r["layers"] for r in rows)
+    print(f"\nall layers: fused {tot_f / 1e3:.2f} ms, unfused {tot_u / 1e3:.2f} ms (fused/unfused {tot_f / tot_u:.2f})")
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+    return 0
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--arch", default="mobilenet_v2")
@@ -138,6 +175,9 @@ def main():
     p.add_argument("--native-only", action="store_true", help="time the native arm alone (A/B of kernel builds)")
     p.add_argument("--list", action="store_true", help="print the layer shapes and the byte counts only (no GPU)")
     p.add_argument("--resources", action="store_true", help="print the compile-time resource table (no GPU)")
+    p.add_argument("--stats", action="store_true",
+                   help="time the forward with the BatchNorm-statistics epilogue (pwconv_fwd_stats: the GEMM and the "
+                        "partial-row fold) against pwconv_fwd followed by bnact_stats (all their launches)")
     p.add_argument("--json", default="", help="also write the rows to this file")
     a = p.parse_args()
 
@@ -157,6 +197,8 @@ def main():
     torch.backends.cudnn.benchmark = bool(a.benchmark)  # 1: MIOpen searches for its fastest algorithm
     torch.manual_seed(0)
     rows = []
+    if a.stats:
+        return stats_table(a, shapes, pw, dev, dt)
     print(f"## {a.arch} @ {a.image_size}, batch {a.bs}, {a.dtype}: native pwconv vs MIOpen\n")
     print("| H_in | C -> K | layers | pass | native us | MIOpen us | native/MIOpen | MB moved | native TB/s | share of 6.3 TB/s |")
     print("|---|---|---|---|---|---|---|---|---|---|")

@@ -24,6 +24,9 @@ p.add_argument("--native-pointwise", default="off", choices=["off", "on"],
                help="on: qualifying 1x1 convs run on the native HIP kernels (ops/pointwise.py); off: MIOpen")
 p.add_argument("--native-stem", default="off", choices=["off", "on"],
                help="on: a qualifying 3x3/2 first conv runs on the native HIP kernels (ops/stemconv.py); off: MIOpen")
+p.add_argument("--native-convstats", default="off", choices=["off", "on"],
+               help="on (with --native-pointwise on and --native-bnact on): converted 1x1 convs emit the statistics of "
+                    "the BatchNorm behind them (ops/convstats.py); off: the BatchNorm reads the conv output for them")
 a = p.parse_args()
 torch.backends.cudnn.benchmark = bool(a.benchmark)
 import threading
@@ -58,6 +61,14 @@ if a.native_bnact == "on":
     from pytorch_distributed_template_amd.ops.bnact import convert_bnact
     n_bn, n_act = convert_bnact(m)
     print(f"native bnact: {n_bn} BatchNorm(s) converted, {n_act} activation(s) fused", flush=True)
+n_cs = 0
+if a.native_convstats == "on":
+    if a.native_pointwise != "on" or a.native_bnact != "on":
+        print("native convstats: ignored, it needs --native-pointwise on and --native-bnact on", flush=True)
+    else:
+        from pytorch_distributed_template_amd.ops.convstats import convert_convstats
+        n_cs = convert_convstats(m)
+        print(f"native convstats: {n_cs} conv/BatchNorm pair(s) fused", flush=True)
 if a.cl:
     m = m.to(memory_format=torch.channels_last)
 opt = torch.optim.SGD(m.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4)
@@ -90,5 +101,6 @@ print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last":
                   "native_depthwise": a.native_depthwise, "depthwise_converted": n_dw,
                   "native_pointwise": a.native_pointwise, "pointwise_converted": n_pw,
                   "native_stem": a.native_stem, "stem_converted": n_stem,
-                  "native_bnact": a.native_bnact, "bnact_converted": n_bn, "bnact_fused": n_act, "ms_per_step": el * 1e3,
+                  "native_bnact": a.native_bnact, "bnact_converted": n_bn, "bnact_fused": n_act,
+                  "native_convstats": a.native_convstats, "convstats_pairs": n_cs, "ms_per_step": el * 1e3,
                   "img_per_s": a.bs / el, "max_mem_GB": torch.cuda.max_memory_allocated() / 1e9}))
