@@ -28,6 +28,7 @@
 #include "kernels/conv_l1.h"
 #include "kernels/conv_wgrad.h"
 #include "kernels/dwconv.h"
+#include "kernels/dwconv7.h"
 #include "kernels/fp32.h"
 #include "kernels/loss.h"
 #include "kernels/optim.h"
@@ -953,6 +954,63 @@ int64_t dwconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, i
   return p.splits;
 }
 
+// ------------------------------------------------------- 7x7 depthwise convolution (dwconv7.hip)
+// groups == Cin == Cout == C, kernel 7x7, stride 1, pad 3, optional bias[C]; x / y / dy / dx NHWC 16-bit of one shape,
+// w [7][7][C] 16-bit (taps-major); the caller allocates
+int dw7_geom(const char* op, const Tensor& a, const Tensor& b, const Tensor* w, int64_t N, int64_t H, int64_t W,
+             int64_t C) {
+  const int dt = dt16(a, op);
+  TORCH_CHECK(dt16(b, op) == dt && (w == nullptr || dt16(*w, op) == dt), op, ": mixed dtypes");
+  TORCH_CHECK(C > 0 && C % 8 == 0, op, ": C must be a positive multiple of 8, got ", C);
+  TORCH_CHECK(N >= 0 && N <= 65535 && H > 0 && W > 0 && H * W * C < (int64_t(1) << 31), op,
+              ": at most 65535 images of fewer than 2^31 elements each");
+  TORCH_CHECK(a.numel() == N * H * W * C && b.numel() == N * H * W * C, op, ": the [N][H][W][C] operands hold ",
+              a.numel(), " and ", b.numel(), " elements, geometry needs ", N * H * W * C);
+  TORCH_CHECK(w == nullptr || w->numel() == 49 * C, op, ": w must hold [7][7][C] = ", 49 * C, " elements");
+  return dt;
+}
+
+void dwconv7_fwd(const Tensor& x, const Tensor& w, const OptT& bias, Tensor& y, int64_t N, int64_t H, int64_t W,
+                 int64_t C) {
+  const int dt = dw7_geom("dwconv7_fwd", x, y, &w, N, H, W, C);
+  TORCH_CHECK(!bias.has_value() || (dt16(*bias, "bias") == dt && bias->numel() == C),
+              "dwconv7_fwd: bias must hold C elements of the activations' dtype");
+  pdt::dwconv7_fwd_launch(dt, p16(x, "x"), p16(w, "w"), p16o(bias, "bias"), p16(y, "y"), N, (int)H, (int)W, (int)C,
+                          cur_stream());
+  launched("dwconv7_fwd");
+}
+
+void dwconv7_dgrad(const Tensor& dy, const Tensor& w, Tensor& dx, int64_t N, int64_t H, int64_t W, int64_t C) {
+  const int dt = dw7_geom("dwconv7_dgrad", dy, dx, &w, N, H, W, C);
+  pdt::dwconv7_dgrad_launch(dt, p16(dy, "dy"), p16(w, "w"), p16(dx, "dx"), N, (int)H, (int)W, (int)C, cur_stream());
+  launched("dwconv7_dgrad");
+}
+
+// (splits, pix_per_split, channel groups): the caller allocates ws = [splits][50][C] fp32
+std::vector<int64_t> dwconv7_wgrad_plan(int64_t npix, int64_t C, int64_t target_blocks) {
+  TORCH_CHECK(C > 0 && C % 8 == 0 && npix >= 0 && npix < (int64_t(1) << 30) && target_blocks >= 1 &&
+                  target_blocks < (int64_t(1) << 30),
+              "dwconv7_wgrad_plan: bad arguments");
+  const pdt::Dw7WgradPlan p = pdt::dwconv7_wgrad_plan(npix, (int)C, (int)target_blocks);
+  return {p.splits, p.pix_per_split, p.groups};
+}
+
+// partial slabs ws[splits][50][C] (fp32: 49 taps, then the sum of dy) for the plan of `target_blocks`; returns the
+// split count to pass to wgrad_reduce (rows = 50, cols = C)
+int64_t dwconv7_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, int64_t H, int64_t W, int64_t C,
+                      int64_t target_blocks) {
+  const int dt = dw7_geom("dwconv7_wgrad", x, dy, nullptr, N, H, W, C);
+  const int64_t npix = N * H * W;
+  TORCH_CHECK(npix > 0 && npix < (int64_t(1) << 30), "dwconv7_wgrad: N * H * W must be in [1, 2^30)");
+  TORCH_CHECK(target_blocks >= 1 && target_blocks < (int64_t(1) << 30), "dwconv7_wgrad: bad target_blocks");
+  const pdt::Dw7WgradPlan p = pdt::dwconv7_wgrad_plan(npix, (int)C, (int)target_blocks);
+  TORCH_CHECK(ws.numel() >= (int64_t)p.splits * 50 * C, "dwconv7_wgrad: ws holds ", ws.numel(),
+              " floats, the plan needs ", (int64_t)p.splits * 50 * C);
+  pdt::dwconv7_wgrad_launch(dt, p16(x, "x"), p16(dy, "dy"), pf(ws, "ws"), N, (int)H, (int)W, (int)C, p, cur_stream());
+  launched("dwconv7_wgrad");
+  return p.splits;
+}
+
 // ------------------------------------------------------- pointwise (1x1) convolution (pwconv.hip)
 // 1x1, stride 1, pad 0, groups 1, no bias; x / y / dy / dx NHWC 16-bit seen as [M][channels], w [K][C] 16-bit
 // (the backward data takes w^T as a [C][K] tensor).  C % 8 == K % 8 == 0, 8 <= C, K <= 2048.
@@ -1768,6 +1826,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv_wgrad_plan", &dwconv_wgrad_plan, py::arg("npix"), py::arg("C"), py::arg("R"), py::arg("target_blocks"));
   m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("N"), py::arg("H"),
         py::arg("W"), py::arg("C"), py::arg("R"), py::arg("stride"), py::arg("target_blocks"));
+  m.def("dwconv7_fwd", &dwconv7_fwd, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("C"));
+  m.def("dwconv7_dgrad", &dwconv7_dgrad, py::arg("dy"), py::arg("w"), py::arg("dx"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("C"));
+  m.def("dwconv7_wgrad_plan", &dwconv7_wgrad_plan, py::arg("npix"), py::arg("C"), py::arg("target_blocks"));
+  m.def("dwconv7_wgrad", &dwconv7_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("target_blocks"));
   m.def("pwconv_fits", &pwconv_fits, py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd_stats", &pwconv_fwd_stats, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("slots"), py::arg("M"),

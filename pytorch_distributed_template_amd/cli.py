@@ -180,6 +180,11 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
                         "followed by its converted BatchNorm inside an nn.Sequential forms the BatchNorm statistics in "
                         "its own epilogue, so the BatchNorm does not read the conv output again for them; ignored "
                         "when either of the two conversions is off or ignored")
+    g.add_argument("--native-dw7", default="off", choices=["off", "on"],
+                   help="torch engine: run qualifying 7x7 depthwise convs (stride 1, padding 3, with or without bias, "
+                        "channels % 8 == 0: ConvNeXt's block conv) on the native HIP kernels where the activations are "
+                        "channels_last GPU tensors, 16-bit or fp32 under 16-bit autocast; elsewhere (CPU, fp32 without "
+                        "autocast, validation) the modules fall back to F.conv2d")
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

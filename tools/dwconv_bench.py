@@ -1,15 +1,17 @@
-"""Per-layer timing of the native depthwise-conv kernels (csrc/kernels/dwconv.hip) against MIOpen.
+"""Per-layer timing of the native depthwise-conv kernels (csrc/kernels/dwconv.hip, dwconv7.hip) against MIOpen.
 
 For every distinct qualifying depthwise layer of ``--arch`` at ``--image-size`` (found by forward hooks on a CPU pass) and
 each pass (forward, backward data, weight gradient) it times, alternating within this process,
 
-* native: ``ops.depthwise.dwconv_fwd / dwconv_dgrad / dwconv_wgrad``
-* MIOpen: ``F.conv2d(groups=C)`` and its autograd on ``channels_last`` tensors of the same dtype
+* native: ``ops.depthwise.dwconv_fwd / dwconv_dgrad / dwconv_wgrad``; for a 7x7 layer (``--arch convnext_tiny``:
+  56x56x96 x3, 28x28x192 x3, 14x14x384 x9, 7x7x768 x3) ``ops.depthwise7.dwconv7_fwd`` with bias ``/ dwconv7_dgrad /
+  dwconv7_wgrad`` with the bias gradient
+* MIOpen: ``F.conv2d(groups=C)`` (with bias for 7x7) and its autograd on ``channels_last`` tensors of the same dtype
 
 with device events around windows of repeated calls after a warm-up, and reports microseconds per call for both
 arms, the bytes the pass has to move (forward / backward data: read one activation, write one; weight gradient: read
-two), the native kernel's achieved TB/s and its share of the HBM ceiling.  ``--resources`` adds each dwconv kernel's
-VGPR / scratch / occupancy figures from the compile-time resource report (needs hipcc, no GPU).
+two), the native kernel's achieved TB/s and its share of the HBM ceiling.  ``--resources`` prints each dwconv and
+dwconv7 kernel's VGPR / scratch / occupancy / LDS figures from the compile-time resource report (needs hipcc, no GPU).
 
 Not part of the framework: a measurement tool only.  Output: a markdown table on stdout, optionally ``--json FILE``.
 """
@@ -33,7 +35,9 @@ HBM_TBS = 6.3  # achievable HBM streaming rate of an MI355X the shares are quote
 def layer_shapes(arch, size):
     """[(H_in, W_in, C, R, stride, count)] of the qualifying depthwise convs, in network order, distinct."""
     from pytorch_distributed_template_amd.models import registry
-    from pytorch_distributed_template_amd.ops.depthwise import qualifies
+    from pytorch_distributed_template_amd.ops.depthwise import qualifies as q35
+    from pytorch_distributed_template_amd.ops.depthwise7 import qualifies7
+    qualifies = lambda m: q35(m) or qualifies7(m)
     model = registry.create(arch).eval()
     seen = {}
 
@@ -55,14 +59,14 @@ def pass_bytes(N, H, W, C, st, esize=2):
     return {"fwd": big + small, "dgrad": big + small, "wgrad": big + small}
 
 
-def kernel_resources():
-    """{kernel name: (VGPRs, AGPRs, scratch bytes/lane, occupancy waves/SIMD, LDS bytes)} of every dwconv kernel, from
-    ``hipcc -Rpass-analysis=kernel-resource-usage`` with the build's device flags."""
+def kernel_resources(source="dwconv.hip"):
+    """{kernel name: (VGPRs, AGPRs, scratch bytes/lane, occupancy waves/SIMD, LDS bytes)} of every kernel of
+    ``source``, from ``hipcc -Rpass-analysis=kernel-resource-usage`` with the build's device flags."""
     from pytorch_distributed_template_amd.ops import _build
     hipcc = shutil.which("hipcc") or os.path.join(_build.ROCM, "bin", "hipcc")
     cmd = [hipcc, f"--offload-arch={_build.ARCH}", "-O3", "-std=c++17", "-ffp-contract=fast", "-munsafe-fp-atomics",
            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", f"-I{_build.CSRC}", "--cuda-device-only", "-c",
-           os.path.join(_build.CSRC, "kernels", "dwconv.hip"), "-o", os.devnull,
+           os.path.join(_build.CSRC, "kernels", source), "-o", os.devnull,
            "-Rpass-analysis=kernel-resource-usage"] + os.environ.get("PDT_HIP_EXTRA", "").split()
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -82,12 +86,17 @@ def kernel_resources():
 
 def demangle(sym):
     """dwconv_strip_kernel<bf16, 3x3, stride 1, flip> style name from the mangled template instance."""
-    m = re.search(r"(dwconv_\w+?_kernel)I((?:L[ib]\d+E)+)E", sym)
+    m = re.search(r"(dwconv7?_\w+?_kernel)I((?:L[ib]\d+E)+)E", sym)
     if not m:
         return sym
     a = [int(v) for v in re.findall(r"L[ib](\d+)E", m.group(2))]
     name = m.group(1)
     dt = "bf16" if a[0] == 0 else "fp16"
+    if name == "dwconv7_tile_kernel":
+        return (f"tile7<{dt}, {a[2]} columns x {a[3]} channel vectors"
+                f"{', flipped taps (dgrad)' if a[4] else ''}{', bias' if a[5] else ''}>")
+    if name == "dwconv7_wgrad_kernel":
+        return f"wgrad7<{dt}>"
     if name == "dwconv_strip_kernel":
         return f"strip<{dt}, {a[1]}x{a[1]}, stride {a[2]}{', flipped taps (dgrad)' if a[3] else ''}>"
     if name == "dwconv_dgrad2_kernel":
@@ -145,7 +154,7 @@ def main():
     a = p.parse_args()
 
     if a.resources:
-        print(resources_md(kernel_resources()))
+        print(resources_md({**kernel_resources(), **kernel_resources("dwconv7.hip")}))
         return 0
     shapes = layer_shapes(a.arch, a.image_size)
     if a.list:
@@ -155,7 +164,7 @@ def main():
     if not torch.cuda.is_available():
         print("dwconv_bench: no GPU (timings are measured, never estimated)", file=sys.stderr)
         return 2
-    from pytorch_distributed_template_amd.ops import depthwise as dw
+    from pytorch_distributed_template_amd.ops import depthwise as dw, depthwise7 as dw7
     dev, dt = torch.device("cuda:0"), {"bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
     torch.backends.cudnn.benchmark = bool(a.benchmark)  # 1: MIOpen searches for its fastest algorithm
     torch.manual_seed(0)
@@ -172,7 +181,15 @@ def main():
         xn, dyn = x.permute(0, 3, 1, 2), dy.permute(0, 3, 1, 2)  # channels_last NCHW views of the same storage
         wn = w.permute(2, 0, 1).unsqueeze(1).contiguous()        # [C, 1, R, S]
         kw = dict(stride=st, padding=R // 2, groups=C)
-        arms = {
+        b = torch.randn(C, device=dev).to(dt) if R == 7 else None  # the 7x7 convs (ConvNeXt) carry a bias
+        bwd = lambda mask: torch.ops.aten.convolution_backward(dyn, xn, wn, [C] if R == 7 else None, [st, st],
+                                                               [R // 2] * 2, [1, 1], False, [0, 0], C, mask)
+        arms7 = {
+            "fwd": (lambda: dw7.dwconv7_fwd(x, w, b), lambda: F.conv2d(xn, wn, b, **kw)),
+            "dgrad": (lambda: dw7.dwconv7_dgrad(dy, w), lambda: bwd([True, False, False])),
+            "wgrad": (lambda: dw7.dwconv7_wgrad(x, dy, True), lambda: bwd([False, True, True])),
+        }
+        arms = arms7 if R == 7 else {
             "fwd": (lambda: dw.dwconv_fwd(x, w, st), lambda: F.conv2d(xn, wn, **kw)),
             "dgrad": (lambda: dw.dwconv_dgrad(dy, w, H, W, st),
                       lambda: torch.ops.aten.convolution_backward(dyn, xn, wn, None, [st, st], [R // 2] * 2, [1, 1], False,

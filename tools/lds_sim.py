@@ -96,10 +96,31 @@ def conv_fwd_generic():
         print(f"conv_fwd ROWB={ROWB}: worst {worst}")
 
 
+def dwconv7():
+    # tile kernel (csrc/kernels/dwconv7.hip): lane = column * CVB + channel vector reads
+    # halo[(row * (TW + 6) + column + s) * CVB + channel vector]: consecutive lanes, consecutive 16 bytes
+    worst_t = 0
+    for tw, cvb in ((32, 8), (16, 16), (8, 32)):
+        for w in range(4):
+            for j in (0, 5):
+                for s in range(7):
+                    addrs = [((j * (tw + 6) + (w * 64 + l) // cvb + s) * cvb + (w * 64 + l) % cvb) * 16 for l in range(64)]
+                    worst_t = max(worst_t, cycles_b128(addrs))
+    # weight gradient: lane = slot * 8 + channel vector reads x row i + slot, column c,
+    # rows `pitch` bytes apart: 21 * 128 as built, 20 * 128 unpadded
+    worst_w = {}
+    for pitch in (21 * 128, 20 * 128):
+        worst_w[pitch] = max(cycles_b128([(i + (l >> 3)) * pitch + c * 128 + (l & 7) * 16 for l in range(64)])
+                             for i in range(8) for c in range(20))
+    print(f"dwconv7: tile halo worst {worst_t} cycles; wgrad x rows worst {worst_w[21 * 128]} at a 2688-byte pitch, "
+          f"{worst_w[20 * 128]} at 2560 (4 = conflict-free)")
+
+
 if __name__ == "__main__":
     conv_l1()
     stem()
     conv_fwd_generic()
+    dwconv7()
 
 
 def stem_search():
