@@ -30,6 +30,7 @@
 #include "kernels/dwconv.h"
 #include "kernels/dwconv7.h"
 #include "kernels/fp32.h"
+#include "kernels/layernorm.h"
 #include "kernels/loss.h"
 #include "kernels/optim.h"
 #include "kernels/pool.h"
@@ -1011,6 +1012,77 @@ int64_t dwconv7_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t N, 
   return p.splits;
 }
 
+// ------------------------------------------------------- LayerNorm (layernorm.hip)
+// dense [rows][C] normalised over C: C % 8 == 0, 8 <= C <= 2048, rows * C < 2^40.  x is 16-bit (the dtype of y) or
+// fp32; y / dy 16-bit; dx the dtype of x; gamma / beta / mean / rstd / partials fp32; the caller allocates
+pdt::LnPlan ln_plan(const char* op, int64_t rows, int64_t C, int64_t max_blocks) {
+  TORCH_CHECK(C >= 8 && C <= 2048 && C % 8 == 0, op, ": C must be a multiple of 8 in [8, 2048], got ", C);
+  TORCH_CHECK(rows >= 1 && rows * C < (int64_t(1) << 40), op, ": rows >= 1 and rows * C < 2^40, got rows = ", rows);
+  TORCH_CHECK(max_blocks >= 1 && max_blocks < (int64_t(1) << 30), op, ": bad max_blocks");
+  return pdt::layernorm_plan(rows, (int)C, (int)max_blocks);
+}
+
+// the activation's data pointer and whether it is fp32: a 16-bit one must have the dtype code `dt`
+const void* ln_act(const char* op, const Tensor& t, const char* name, int dt, int64_t numel, bool* f32) {
+  check_dev(t, name);
+  *f32 = t.scalar_type() == at::kFloat;
+  TORCH_CHECK(*f32 || dt16(t, name) == dt, op, ": ", name, " must be float32 or the 16-bit dtype of y / dy");
+  TORCH_CHECK(t.numel() == numel, op, ": ", name, " holds ", t.numel(), " elements, rows * C = ", numel);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
+  return t.data_ptr();
+}
+
+float* ln_vec(const char* op, const Tensor& t, const char* name, int64_t n) {
+  TORCH_CHECK(t.numel() == n, op, ": ", name, " must hold ", n, " floats, holds ", t.numel());
+  return pf(t, name);
+}
+
+// (L, NV, blocks): lanes per row, 8-channel vectors per lane, persistent blocks (= partial rows of the backward)
+std::vector<int64_t> layernorm_plan(int64_t rows, int64_t C, int64_t max_blocks) {
+  const pdt::LnPlan p = ln_plan("layernorm_plan", rows, C, max_blocks);
+  return {p.L, p.NV, p.blocks};
+}
+
+void layernorm_fwd(const Tensor& x, const Tensor& gamma, const OptT& beta, Tensor& y, Tensor& mean, Tensor& rstd,
+                   int64_t rows, int64_t C, double eps, int64_t max_blocks) {
+  const char* op = "layernorm_fwd";
+  const pdt::LnPlan p = ln_plan(op, rows, C, max_blocks);
+  const int dt = dt16(y, "y");
+  bool xf = false, yf = false;
+  const void* xp = ln_act(op, x, "x", dt, rows * C, &xf);
+  ln_act(op, y, "y", dt, rows * C, &yf);
+  const float* bp = beta.has_value() ? ln_vec(op, *beta, "beta", C) : nullptr;
+  pdt::layernorm_fwd_launch(dt, xf, xp, ln_vec(op, gamma, "gamma", C), bp, p16(y, "y"),
+                            ln_vec(op, mean, "mean", rows), ln_vec(op, rstd, "rstd", rows), rows, (int)C, (float)eps,
+                            p, cur_stream());
+  launched("layernorm_fwd");
+}
+
+// dx, and when `partials` is given the gamma / beta gradient partials [blocks][2][C] (row 0: sum of dy * xhat, row 1:
+// sum of dy) for the plan of `max_blocks`; returns the number of partial rows written (0 without `partials`), to be
+// summed with wgrad_reduce
+int64_t layernorm_bwd(const Tensor& dy, const Tensor& x, const Tensor& mean, const Tensor& rstd, const Tensor& gamma,
+                      Tensor& dx, const OptT& partials, int64_t rows, int64_t C, int64_t max_blocks) {
+  const char* op = "layernorm_bwd";
+  const pdt::LnPlan p = ln_plan(op, rows, C, max_blocks);
+  const int dt = dt16(dy, "dy");
+  bool xf = false, dxf = false, dyf = false;
+  const void* xp = ln_act(op, x, "x", dt, rows * C, &xf);
+  ln_act(op, dy, "dy", dt, rows * C, &dyf);
+  void* dxp = const_cast<void*>(ln_act(op, dx, "dx", dt, rows * C, &dxf));
+  TORCH_CHECK(dxf == xf, op, ": dx must have the dtype of x");
+  float* pp = nullptr;
+  if (partials.has_value()) {
+    TORCH_CHECK(partials->numel() >= (int64_t)p.blocks * 2 * C, op, ": partials holds ", partials->numel(),
+                " floats, the plan needs ", (int64_t)p.blocks * 2 * C);
+    pp = pf(*partials, "partials");
+  }
+  pdt::layernorm_bwd_launch(dt, xf, p16(dy, "dy"), xp, ln_vec(op, mean, "mean", rows), ln_vec(op, rstd, "rstd", rows),
+                            ln_vec(op, gamma, "gamma", C), dxp, pp, rows, (int)C, p, cur_stream());
+  launched("layernorm_bwd");
+  return pp ? p.blocks : 0;
+}
+
 // ------------------------------------------------------- pointwise (1x1) convolution (pwconv.hip)
 // 1x1, stride 1, pad 0, groups 1, no bias; x / y / dy / dx NHWC 16-bit seen as [M][channels], w [K][C] 16-bit
 // (the backward data takes w^T as a [C][K] tensor).  C % 8 == K % 8 == 0, 8 <= C, K <= 2048.
@@ -1833,6 +1905,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv7_wgrad_plan", &dwconv7_wgrad_plan, py::arg("npix"), py::arg("C"), py::arg("target_blocks"));
   m.def("dwconv7_wgrad", &dwconv7_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("N"), py::arg("H"),
         py::arg("W"), py::arg("C"), py::arg("target_blocks"));
+  m.def("layernorm_plan", &layernorm_plan, py::arg("rows"), py::arg("C"), py::arg("max_blocks"));
+  m.def("layernorm_fwd", &layernorm_fwd, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("mean"),
+        py::arg("rstd"), py::arg("rows"), py::arg("C"), py::arg("eps"), py::arg("max_blocks"));
+  m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"), py::arg("mean"), py::arg("rstd"),
+        py::arg("gamma"), py::arg("dx"), py::arg("partials"), py::arg("rows"), py::arg("C"), py::arg("max_blocks"));
   m.def("pwconv_fits", &pwconv_fits, py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd_stats", &pwconv_fwd_stats, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("slots"), py::arg("M"),

@@ -185,6 +185,12 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
                         "channels % 8 == 0: ConvNeXt's block conv) on the native HIP kernels where the activations are "
                         "channels_last GPU tensors, 16-bit or fp32 under 16-bit autocast; elsewhere (CPU, fp32 without "
                         "autocast, validation) the modules fall back to F.conv2d")
+    g.add_argument("--native-layernorm", default="off", choices=["off", "on"],
+                   help="torch engine: run qualifying LayerNorms (one normalised dimension C, C % 8 == 0, "
+                        "8 <= C <= 2048, elementwise_affine: every ConvNeXt, ViT and Swin block) on the native HIP "
+                        "kernels where the input is a dense GPU tensor under 16-bit autocast; the result then has the "
+                        "autocast dtype (fp32 LayerNorm, rounded once) instead of fp32; elsewhere (CPU, no autocast, "
+                        "validation, strided inputs) the modules fall back to F.layer_norm")
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

@@ -350,6 +350,10 @@ def main(mode: str, argv: Optional[list] = None) -> int:
     if getattr(args, "native_dw7", "off") == "on" and engine == "torch":
         from ..ops.depthwise7 import convert_depthwise7
         ddp_print("=> native dw7: {} conv(s) of {} converted".format(convert_depthwise7(model), args.arch), logger, rank)
+    if getattr(args, "native_layernorm", "off") == "on" and engine == "torch":
+        from ..ops.layernorm import convert_layernorm
+        ddp_print("=> native layernorm: {} LayerNorm(s) of {} converted".format(convert_layernorm(model), args.arch),
+                  logger, rank)
     if getattr(args, "native_bnact", "off") == "on" and engine == "torch":
         if distributed and bool(getattr(args, "sync_batchnorm", False)):
             # the trainer's condition for SyncBatchNorm.convert_sync_batchnorm, which rebuilds every _BatchNorm

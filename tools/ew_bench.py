@@ -4,6 +4,8 @@ activation timed alternately in the same process.
 
     python tools/ew_bench.py [--so A.so B.so ...]   # one subprocess per build of the extension (PDT_NATIVE_SO)
     python tools/ew_bench.py --bnact [--batch 400] [--act relu6]
+    python tools/ew_bench.py --layernorm [--batch 128] [--max-blocks 1024]   # PDT_LN_TIGHT=1: the other (L, NV) rule
+    python tools/ew_bench.py --layernorm --resources                          # VGPRs / scratch / occupancy, no GPU
 
 (Round 5 chose 4 vectors per thread with this script: csrc/kernels/bn.hip kEwU.)
 
@@ -12,6 +14,8 @@ Prints one JSON line per (U, pass, shape): microseconds and TB/s of the bytes th
 import argparse
 import json
 import os
+import re
+import shutil
 import subprocess
 import sys
 
@@ -138,23 +142,122 @@ def child_bnact(batch, act):
                               "torch_us": round(ut, 1), "torch_over_bnact": round(ut / us, 2)}), flush=True)
         del x, g, o, xt, gt, yt
 
+# the LayerNorm inputs of convnext_tiny at 224 x 224: (H = W, C, x is fp32, how many).  Block norms and the stem norm
+# read a 16-bit conv output, the downsample and classifier norms the fp32 residual stream.
+LN_SHAPES = [(56, 96, False, 4), (56, 96, True, 1), (28, 192, False, 3), (28, 192, True, 1), (14, 384, False, 9),
+             (14, 384, True, 1), (7, 768, False, 3), (1, 768, True, 1)]
+
+
+def child_layernorm(batch, max_blocks):
+    """Per layer, forward and backward: the native kernels against F.layer_norm under autocast with the casts
+    autocast and the consumer make (16-bit x -> fp32, fp32 y -> 16-bit, and their backward), the two arms alternating
+    rep by rep, median of three windows.  Bytes: what one pass must move (x, y / dy, x, dx)."""
+    import torch
+    import torch.nn.functional as F
+    sys.path.insert(0, ROOT)
+    from pytorch_distributed_template_amd.ops import layernorm as ln
+    dev, dt = "cuda", torch.bfloat16
+    rule = "tight" if os.environ.get("PDT_LN_TIGHT") == "1" else "wide"
+
+    def alternate(f_ours, f_torch, reps=20):
+        for _ in range(3):
+            f_ours(), f_torch()
+        wins = []
+        for _ in range(3):
+            ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(reps)]
+            for e in ev:
+                e[0].record()
+                f_ours()
+                e[1].record()
+                f_torch()
+                e[2].record()
+            torch.cuda.synchronize()
+            wins.append((sorted(e[0].elapsed_time(e[1]) for e in ev)[reps // 2] * 1e3,
+                         sorted(e[1].elapsed_time(e[2]) for e in ev)[reps // 2] * 1e3))
+        return sorted(w[0] for w in wins)[1], sorted(w[1] for w in wins)[1]
+
+    tot = {"fwd": [0.0, 0.0], "bwd": [0.0, 0.0]}
+    for hw, c, xf32, count in LN_SHAPES:
+        rows = batch * hw * hw
+        n, xb = rows * c, 4 if xf32 else 2
+        x = torch.randn(rows, c, device=dev).to(torch.float32 if xf32 else dt)
+        dy = torch.randn(rows, c, device=dev).to(dt)
+        g, b = torch.rand(c, device=dev) + 0.5, torch.randn(c, device=dev)
+        xt, gt, bt = (v.clone().requires_grad_(True) for v in (x, g, b))
+
+        def t_fwd():
+            with torch.autocast("cuda", dtype=dt):
+                return F.layer_norm(xt, (c,), gt, bt, 1e-6).to(dt)
+        yt = t_fwd()
+        _, mean, rstd = ln.layernorm_fwd(x, g, b, 1e-6, dt, max_blocks)
+        passes = (("fwd", lambda: ln.layernorm_fwd(x, g, b, 1e-6, dt, max_blocks), t_fwd, xb + 2),
+                  ("bwd", lambda: ln.layernorm_bwd(dy, x, mean, rstd, g, True, max_blocks),
+                   lambda: torch.autograd.grad(yt, (xt, gt, bt), dy, retain_graph=True), 2 + 2 * xb))
+        for name, fo, ft, bpe in passes:
+            us, ut = alternate(fo, ft)
+            tot[name][0] += us * count
+            tot[name][1] += ut * count
+            print(json.dumps({"pass": name, "rule": rule, "plan": ln.layernorm_plan(rows, c, max_blocks), "B": batch,
+                              "rows": rows, "C": c, "x": "fp32" if xf32 else "bf16", "count": count,
+                              "native_us": round(us, 1), "torch_us": round(ut, 1), "torch_over_native": round(ut / us, 2),
+                              "MB": round(bpe * n / 1e6, 1), "TB_s": round(bpe * n / us / 1e6, 2),
+                              "of_6.3": round(bpe * n / us / 1e6 / 6.3, 2)}), flush=True)
+        del x, dy, xt, yt
+    print(json.dumps({"rule": rule, "max_blocks": max_blocks, "all_23_layers_ms": {
+        k: {"native": round(v[0] / 1e3, 3), "torch": round(v[1] / 1e3, 3)} for k, v in tot.items()}}), flush=True)
+
+
+def layernorm_resources():
+    """VGPRs / AGPRs / scratch / occupancy / LDS of every layernorm.hip kernel from the compiler's resource report
+    (needs hipcc, no GPU), as a markdown table."""
+    sys.path.insert(0, ROOT)
+    from pytorch_distributed_template_amd.ops import _build
+    hipcc = shutil.which("hipcc") or os.path.join(_build.ROCM, "bin", "hipcc")
+    cmd = [hipcc, f"--offload-arch={_build.ARCH}", "-O3", "-std=c++17", "-ffp-contract=fast", "-munsafe-fp-atomics",
+           "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", f"-I{_build.CSRC}", "--cuda-device-only", "-c",
+           os.path.join(_build.CSRC, "kernels", "layernorm.hip"), "-o", os.devnull,
+           "-Rpass-analysis=kernel-resource-usage"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(r.stderr[-2000:])
+    print("| kernel | x | NV | gamma / beta sums | VGPRs | AGPRs | scratch B/lane | occupancy waves/SIMD | LDS B/block |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for blk in re.split(r"Function Name: ", r.stderr)[1:]:
+        m = re.match(r"\S*layernorm_(fwd|bwd)_kernelILi(\d)ELb(\d)ELi(\d)E(?:Lb(\d)E)?", blk)
+        if not m:
+            continue
+        v = [re.search(pat + r": (\d+)", blk).group(1) for pat in (
+            " VGPRs", "AGPRs", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]", r"LDS Size \[bytes/block\]")]
+        sums = {None: "-", "0": "no", "1": "yes"}[m.group(5)]
+        print(f"| {m.group(1)} {('bf16', 'fp16')[int(m.group(2))]} | {('16-bit', 'fp32')[int(m.group(3))]} | "
+              f"{m.group(4)} | {sums} | " + " | ".join(v) + " |")
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--so", nargs="+", default=[""])
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--bnact", action="store_true", help="the four bnact passes at MobileNetV2 shapes instead")
-    ap.add_argument("--batch", type=int, default=400)
+    ap.add_argument("--layernorm", action="store_true", help="the LayerNorm kernels at convnext_tiny shapes instead")
+    ap.add_argument("--resources", action="store_true", help="with --layernorm: the kernels' resource table (no GPU)")
+    ap.add_argument("--max-blocks", type=int, default=1024)
+    ap.add_argument("--batch", type=int, default=None, help="default 400 (--bnact), 128 (--layernorm)")
     ap.add_argument("--act", default="relu6", choices=["identity", "relu", "relu6", "hardswish"])
     a = ap.parse_args()
+    a.batch = a.batch or (128 if a.layernorm else 400)
+    if a.layernorm and a.resources:
+        layernorm_resources()
+        return
     if a.child:
-        child_bnact(a.batch, a.act) if a.bnact else child()
+        child_layernorm(a.batch, a.max_blocks) if a.layernorm else child_bnact(a.batch, a.act) if a.bnact else child()
         return
     for so in a.so:
         env = dict(os.environ)
         if so:
             env["PDT_NATIVE_SO"] = so
         extra = ["--bnact", "--batch", str(a.batch), "--act", a.act] if a.bnact else []
+        if a.layernorm:
+            extra = ["--layernorm", "--batch", str(a.batch), "--max-blocks", str(a.max_blocks)]
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + extra, env=env, timeout=600)
         if r.returncode != 0:
             sys.exit(r.returncode)

@@ -29,6 +29,8 @@ p.add_argument("--native-convstats", default="off", choices=["off", "on"],
                     "the BatchNorm behind them (ops/convstats.py); off: the BatchNorm reads the conv output for them")
 p.add_argument("--native-dw7", default="off", choices=["off", "on"],
                help="on: qualifying 7x7 depthwise convs run on the native HIP kernels (ops/depthwise7.py); off: MIOpen")
+p.add_argument("--native-layernorm", default="off", choices=["off", "on"],
+               help="on: qualifying LayerNorms run on the native HIP kernels (ops/layernorm.py); off: F.layer_norm")
 a = p.parse_args()
 torch.backends.cudnn.benchmark = bool(a.benchmark)
 import threading
@@ -63,6 +65,11 @@ if a.native_dw7 == "on":
     from pytorch_distributed_template_amd.ops.depthwise7 import convert_depthwise7
     n_dw7 = convert_depthwise7(m)
     print(f"native dw7: {n_dw7} conv(s) converted", flush=True)
+n_ln = 0
+if a.native_layernorm == "on":
+    from pytorch_distributed_template_amd.ops.layernorm import convert_layernorm
+    n_ln = convert_layernorm(m)
+    print(f"native layernorm: {n_ln} LayerNorm(s) converted", flush=True)
 n_bn = n_act = 0
 if a.native_bnact == "on":
     from pytorch_distributed_template_amd.ops.bnact import convert_bnact
@@ -109,6 +116,7 @@ print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last":
                   "native_pointwise": a.native_pointwise, "pointwise_converted": n_pw,
                   "native_stem": a.native_stem, "stem_converted": n_stem,
                   "native_dw7": a.native_dw7, "dw7_converted": n_dw7,
+                  "native_layernorm": a.native_layernorm, "layernorm_converted": n_ln,
                   "native_bnact": a.native_bnact, "bnact_converted": n_bn, "bnact_fused": n_act,
                   "native_convstats": a.native_convstats, "convstats_pairs": n_cs, "ms_per_step": el * 1e3,
                   "img_per_s": a.bs / el, "max_mem_GB": torch.cuda.max_memory_allocated() / 1e9}))
