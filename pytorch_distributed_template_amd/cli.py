@@ -25,6 +25,7 @@ import os
 from typing import List, Optional
 
 from .models.registry import model_names
+from .ops import conversions
 
 ENTRY_DEFAULTS = {
     "dp": {"gpus": "5,6,7", "outpath": "./output", "logger": "DataParallel"},
@@ -155,42 +156,7 @@ def build_parser(mode: str) -> argparse.ArgumentParser:
     g.add_argument("--autotune", default=False, type=str2bool, nargs="?", const=True,
                    help="time the candidate conv tile configs once per shape and keep the fastest (the analogue of "
                         "the reference's cudnn.benchmark=True); off = the static per-shape table")
-    g.add_argument("--native-depthwise", default="off", choices=["off", "on"],
-                   help="torch engine: run qualifying depthwise convs (3x3 / 5x5, stride 1 / 2, no bias, channels % 8 "
-                        "== 0) on the native HIP depthwise kernels where the activations are 16-bit channels_last "
-                        "GPU tensors; elsewhere (CPU, fp32, validation) the modules fall back to F.conv2d")
-    g.add_argument("--native-bnact", default="off", choices=["off", "on"],
-                   help="torch engine: run qualifying BatchNorm2d layers (affine, running statistics, channels % 8 == 0, "
-                        "<= 2048) fused with the ReLU / ReLU6 / Hardswish that follows them on the native HIP kernels "
-                        "where the training activations are 16-bit channels_last GPU tensors; elsewhere (CPU, fp32, "
-                        "validation) the modules fall back to the stock ops; ignored when --sync_batchnorm converts "
-                        "the model")
-    g.add_argument("--native-pointwise", default="off", choices=["off", "on"],
-                   help="torch engine: run qualifying 1x1 convs (stride 1, padding 0, groups 1, no bias, both channel "
-                        "counts % 8 == 0 and within 8..2048) on the native HIP pointwise kernels where the activations "
-                        "are 16-bit channels_last GPU tensors; elsewhere (CPU, fp32, validation) the modules fall back "
-                        "to F.conv2d")
-    g.add_argument("--native-stem", default="off", choices=["off", "on"],
-                   help="torch engine: run a qualifying first conv (3 input channels, 3x3, stride 2, padding 1, no bias, "
-                        "output channels % 8 == 0 and within 8..64) on the native HIP stem kernels where the image is an "
-                        "fp32 channels_last GPU tensor under 16-bit autocast; elsewhere (CPU, fp32, validation) the "
-                        "module falls back to F.conv2d")
-    g.add_argument("--native-convstats", default="off", choices=["off", "on"],
-                   help="torch engine, with --native-pointwise on and --native-bnact on: a converted 1x1 conv directly "
-                        "followed by its converted BatchNorm inside an nn.Sequential forms the BatchNorm statistics in "
-                        "its own epilogue, so the BatchNorm does not read the conv output again for them; ignored "
-                        "when either of the two conversions is off or ignored")
-    g.add_argument("--native-dw7", default="off", choices=["off", "on"],
-                   help="torch engine: run qualifying 7x7 depthwise convs (stride 1, padding 3, with or without bias, "
-                        "channels % 8 == 0: ConvNeXt's block conv) on the native HIP kernels where the activations are "
-                        "channels_last GPU tensors, 16-bit or fp32 under 16-bit autocast; elsewhere (CPU, fp32 without "
-                        "autocast, validation) the modules fall back to F.conv2d")
-    g.add_argument("--native-layernorm", default="off", choices=["off", "on"],
-                   help="torch engine: run qualifying LayerNorms (one normalised dimension C, C % 8 == 0, "
-                        "8 <= C <= 2048, elementwise_affine: every ConvNeXt, ViT and Swin block) on the native HIP "
-                        "kernels where the input is a dense GPU tensor under 16-bit autocast; the result then has the "
-                        "autocast dtype (fp32 LayerNorm, rounded once) instead of fp32; elsewhere (CPU, no autocast, "
-                        "validation, strided inputs) the modules fall back to F.layer_norm")
+    conversions.add_flags(g)
     g.add_argument("--use-gpus-flag", default=False, type=str2bool, nargs="?", const=True,
                    help="honour --gpus by setting HIP_VISIBLE_DEVICES (the reference ignores --gpus)")
     g.add_argument("--no-tensorboard", dest="tensorboard", action="store_false")

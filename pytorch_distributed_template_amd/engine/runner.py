@@ -30,6 +30,7 @@ from .. import cli
 from ..data.loader import build_loaders
 from ..models import registry
 from ..models.inception import AUX_LOSS_WEIGHT
+from ..ops import conversions
 from ..optim.lr import build_scheduler
 from ..utils.io import load_checkpoint, make_checkpoint_state, output_process, save_checkpoint, write_settings
 from ..utils.logging import close_logger, ddp_print, get_logger
@@ -335,45 +336,11 @@ def main(mode: str, argv: Optional[list] = None) -> int:
 
     ddp_print("=> engine: {} | compute dtype: {} | device: {} | world: {}".format(engine, str(dtype).split(".")[-1],
                                                                                 device, world), logger, rank)
-    if getattr(args, "native_depthwise", "off") == "on" and engine == "torch":
-        # before the trainer flattens the parameters: the converted modules keep the same Parameter objects
-        from ..ops.depthwise import convert_depthwise
-        ddp_print("=> native depthwise: {} conv(s) of {} converted".format(convert_depthwise(model), args.arch),
-                  logger, rank)
-    if getattr(args, "native_pointwise", "off") == "on" and engine == "torch":
-        from ..ops.pointwise import convert_pointwise
-        ddp_print("=> native pointwise: {} conv(s) of {} converted".format(convert_pointwise(model), args.arch),
-                  logger, rank)
-    if getattr(args, "native_stem", "off") == "on" and engine == "torch":
-        from ..ops.stemconv import convert_stem
-        ddp_print("=> native stem: {} conv(s) of {} converted".format(convert_stem(model), args.arch), logger, rank)
-    if getattr(args, "native_dw7", "off") == "on" and engine == "torch":
-        from ..ops.depthwise7 import convert_depthwise7
-        ddp_print("=> native dw7: {} conv(s) of {} converted".format(convert_depthwise7(model), args.arch), logger, rank)
-    if getattr(args, "native_layernorm", "off") == "on" and engine == "torch":
-        from ..ops.layernorm import convert_layernorm
-        ddp_print("=> native layernorm: {} LayerNorm(s) of {} converted".format(convert_layernorm(model), args.arch),
-                  logger, rank)
-    if getattr(args, "native_bnact", "off") == "on" and engine == "torch":
-        if distributed and bool(getattr(args, "sync_batchnorm", False)):
-            # the trainer's condition for SyncBatchNorm.convert_sync_batchnorm, which rebuilds every _BatchNorm
-            # and would drop the absorbed activations
-            ddp_print("=> native bnact: ignored, --sync_batchnorm converts the model's BatchNorms", logger, rank)
-        else:
-            from ..ops.bnact import convert_bnact
-            n_bn, n_absorbed = convert_bnact(model)
-            ddp_print("=> native bnact: {} BatchNorm(s) of {} converted, {} activation(s) fused".format(
-                n_bn, args.arch, n_absorbed), logger, rank)
-    if getattr(args, "native_convstats", "off") == "on" and engine == "torch":
-        # pairs of the two conversions above: it needs both
-        if getattr(args, "native_pointwise", "off") != "on" or getattr(args, "native_bnact", "off") != "on":
-            ddp_print("=> native convstats: ignored, it needs --native-pointwise on and --native-bnact on", logger, rank)
-        elif distributed and bool(getattr(args, "sync_batchnorm", False)):
-            ddp_print("=> native convstats: ignored, --sync_batchnorm converts the model's BatchNorms", logger, rank)
-        else:
-            from ..ops.convstats import convert_convstats
-            ddp_print("=> native convstats: {} conv/BatchNorm pair(s) of {} fused".format(
-                convert_convstats(model), args.arch), logger, rank)
+    if engine == "torch":
+        # before the trainer flattens the parameters: the converted modules keep the same Parameter objects.
+        # syncbn_converts is the trainer's condition for SyncBatchNorm.convert_sync_batchnorm
+        conversions.apply(model, args, args.arch, distributed and bool(getattr(args, "sync_batchnorm", False)),
+                          lambda s: ddp_print(s, logger, rank))
     trainer = build_trainer(mode, model, args, device, dtype, engine, world)
     optimizer = trainer.optimizer
     gn = getattr(args, "gpu_normalize", "off")

@@ -23,11 +23,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import native
+from ._module import DTYPES16, grad_nhwc, nchw, nhwc, reclass
 
 ACTS = ("identity", "relu", "relu6", "hardswish")  # the kernels' activation codes are the indices
 MAX_C = 2048
 
-_DTYPES = (torch.bfloat16, torch.float16)
 _ACT_FN = {"identity": lambda t: t, "relu": F.relu, "relu6": F.relu6, "hardswish": F.hardswish}
 _ACT_OF = {nn.ReLU: "relu", nn.ReLU6: "relu6", nn.Hardswish: "hardswish"}
 
@@ -116,7 +116,7 @@ class _BNActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, act, slots=None):
-        xh = x.permute(0, 2, 3, 1)  # NHWC view of the channels_last storage: no copy
+        xh = nhwc(x)
         if slots is None:
             coef = bnact_stats(xh, gamma.detach(), beta.detach(), running_mean, running_var, eps, momentum)
         else:  # the statistics of x from the conv that produced it: a non-differentiable extra, same autograd
@@ -125,21 +125,18 @@ class _BNActFn(torch.autograd.Function):
         out = bnact_fwd(xh, coef, act)
         ctx.save_for_backward(x, coef, gamma)
         ctx.act = act
-        return out.permute(0, 3, 1, 2)  # channels_last NCHW view
+        return nchw(out)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, coef, gamma = ctx.saved_tensors
-        xh = x.permute(0, 2, 3, 1)
-        g = gy.permute(0, 2, 3, 1)
-        if g.dtype != x.dtype or not g.is_contiguous():
-            g = g.to(x.dtype).contiguous()
+        xh, g = nhwc(x), grad_nhwc(gy, x.dtype)
         sums = bnact_bwd_reduce(g, xh, coef, ctx.act)
         dgamma, dbeta, bcoef = bnact_bwd_coef(sums, xh.numel() // xh.shape[-1], coef, gamma.detach())
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = bnact_bwd_apply(g, xh, coef, bcoef, ctx.act).permute(0, 3, 1, 2)
+            dx = nchw(bnact_bwd_apply(g, xh, coef, bcoef, ctx.act))
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -163,7 +160,7 @@ class BNAct2d(nn.BatchNorm2d):
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         handed = take_conv_stats(input)  # removed whatever path is taken below
-        if (self.training and input.is_cuda and input.dtype in _DTYPES and input.dim() == 4 and qualifies(self)
+        if (self.training and input.is_cuda and input.dtype in DTYPES16 and input.dim() == 4 and qualifies(self)
                 and self.weight.dtype == torch.float32 and input.shape[1] == self.num_features
                 and input.numel() // self.num_features >= 2
                 and input.is_contiguous(memory_format=torch.channels_last)):
@@ -180,16 +177,6 @@ class BNAct2d(nn.BatchNorm2d):
             slots = handed[0]
         return _BNActFn.apply(input, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
                               self.momentum, self.act, slots)
-
-
-def _as_bnact(bn: nn.BatchNorm2d, act: str) -> BNAct2d:
-    # the same module state under the new class: parameters and buffers (the same objects), hooks, training flag
-    new = BNAct2d.__new__(BNAct2d)
-    new.__dict__ = bn.__dict__.copy()
-    for k in ("_parameters", "_buffers", "_modules"):
-        new.__dict__[k] = bn.__dict__[k].copy()
-    new.__dict__["act"] = act
-    return new
 
 
 def convert_bnact(model: nn.Module):
@@ -213,6 +200,6 @@ def convert_bnact(model: nn.Module):
                     act = _ACT_OF[type(nxt)]
                     setattr(parent, nxt_name, nn.Identity())
                     n_abs += 1
-            setattr(parent, name, _as_bnact(child, act))
+            setattr(parent, name, reclass(child, BNAct2d, act=act))
             n_bn += 1
     return n_bn, n_abs

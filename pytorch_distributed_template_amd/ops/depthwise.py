@@ -20,11 +20,10 @@ import torch
 import torch.nn as nn
 
 from . import native
+from ._module import DTYPES16, grad_nhwc, nchw, nhwc, swap_children
 
 # blocks the weight gradient aims for: a few per CU (256 CUs), so the split-K tail stays short
 WGRAD_TARGET_BLOCKS = 2048
-
-_DTYPES = (torch.bfloat16, torch.float16)
 
 
 def _out_size(n: int, stride: int) -> int:
@@ -85,22 +84,19 @@ class _DepthwiseFn(torch.autograd.Function):
         C, _, R, S = weight.shape
         # the 16-bit taps-major operand of the kernels, derived from the master here (not an autograd op)
         w16 = weight.detach().reshape(C, R * S).t().to(x.dtype).contiguous().view(R, S, C)
-        y = dwconv_fwd(x.permute(0, 2, 3, 1), w16, stride)  # NHWC view of the channels_last storage: no copy
+        y = dwconv_fwd(nhwc(x), w16, stride)
         ctx.save_for_backward(x, w16)
         ctx.stride = stride
-        return y.permute(0, 3, 1, 2)  # channels_last NCHW view
+        return nchw(y)
 
     @staticmethod
     def backward(ctx, gy):
         x, w16 = ctx.saved_tensors
         R, S, C = w16.shape
-        g = gy.permute(0, 2, 3, 1)
-        if g.dtype != x.dtype or not g.is_contiguous():
-            g = g.to(x.dtype).contiguous()
-        xh = x.permute(0, 2, 3, 1)
+        g, xh = grad_nhwc(gy, x.dtype), nhwc(x)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = dwconv_dgrad(g, w16, xh.shape[1], xh.shape[2], ctx.stride).permute(0, 3, 1, 2)
+            dx = nchw(dwconv_dgrad(g, w16, xh.shape[1], xh.shape[2], ctx.stride))
         dw = None
         if ctx.needs_input_grad[1]:
             # fp32 all the way: [R, S, C] -> the parameter's [C, 1, R, S]
@@ -114,29 +110,14 @@ class DepthwiseConv2d(nn.Conv2d):
     non-qualifying configurations take ``F.conv2d`` exactly as the parent does."""
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
-        if (input.is_cuda and input.dtype in _DTYPES and input.dim() == 4 and qualifies(self)
+        if (input.is_cuda and input.dtype in DTYPES16 and input.dim() == 4 and qualifies(self)
                 and input.is_contiguous(memory_format=torch.channels_last)):
             return _DepthwiseFn.apply(input, self.weight, self.stride[0])
         return super().forward(input)
-
-
-def _as_depthwise(conv: nn.Conv2d) -> DepthwiseConv2d:
-    # the same module state under the new class: parameters (the same Parameter objects), hooks, training flag
-    new = DepthwiseConv2d.__new__(DepthwiseConv2d)
-    new.__dict__ = conv.__dict__.copy()
-    for k in ("_parameters", "_buffers", "_modules"):
-        new.__dict__[k] = conv.__dict__[k].copy()
-    return new
 
 
 def convert_depthwise(model: nn.Module) -> int:
     """Swap every qualifying ``nn.Conv2d`` below ``model`` for a :class:`DepthwiseConv2d` holding the same
     ``Parameter``; returns how many were swapped (0 on a second call).  Call it before the parameters are
     flattened (``optim.flat.FlatParams``)."""
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if type(child) is nn.Conv2d and qualifies(child):
-                setattr(parent, name, _as_depthwise(child))
-                n += 1
-    return n
+    return swap_children(model, {nn.Conv2d: DepthwiseConv2d}, qualifies)

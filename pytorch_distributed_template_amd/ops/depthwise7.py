@@ -22,11 +22,10 @@ import torch
 import torch.nn as nn
 
 from . import native
+from ._module import DTYPES16, autocast_dtype, grad_nhwc, nchw, nhwc, swap_children
 
 # blocks the weight gradient aims for: a few per CU (256 CUs), so the split tail stays short
 WGRAD_TARGET_BLOCKS = 2048
-
-_DTYPES = (torch.bfloat16, torch.float16)
 
 
 def dwconv7_fwd(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None) -> torch.Tensor:
@@ -80,24 +79,22 @@ class _Depthwise7Fn(torch.autograd.Function):
         # the 16-bit operands of the kernels, derived from the masters here (not autograd ops)
         w16 = weight.detach().reshape(C, 49).t().to(x.dtype).contiguous().view(7, 7, C)
         b16 = None if bias is None else bias.detach().to(x.dtype).contiguous()
-        y = dwconv7_fwd(x.permute(0, 2, 3, 1), w16, b16)  # NHWC view of the channels_last storage: no copy
+        y = dwconv7_fwd(nhwc(x), w16, b16)
         ctx.save_for_backward(x, w16)
         ctx.has_bias = bias is not None
-        return y.permute(0, 3, 1, 2)  # channels_last NCHW view
+        return nchw(y)
 
     @staticmethod
     def backward(ctx, gy):
         x, w16 = ctx.saved_tensors
         C = w16.shape[2]
-        g = gy.permute(0, 2, 3, 1)
-        if g.dtype != x.dtype or not g.is_contiguous():
-            g = g.to(x.dtype).contiguous()
+        g = grad_nhwc(gy, x.dtype)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = dwconv7_dgrad(g, w16).permute(0, 3, 1, 2)
+            dx = nchw(dwconv7_dgrad(g, w16))
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_b:
-            dw, db = dwconv7_wgrad(x.permute(0, 2, 3, 1), g, want_b)
+            dw, db = dwconv7_wgrad(nhwc(x), g, want_b)
             # fp32 all the way: [7, 7, C] -> the parameter's [C, 1, 7, 7]
             dw = dw.reshape(49, C).t().reshape(C, 1, 7, 7) if ctx.needs_input_grad[1] else None
         return dx, dw, db
@@ -113,33 +110,17 @@ class DepthwiseConv7x7(nn.Conv2d):
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         if (input.is_cuda and input.dim() == 4 and qualifies7(self)
                 and input.is_contiguous(memory_format=torch.channels_last)):
-            if input.dtype in _DTYPES:
+            if input.dtype in DTYPES16:
                 return _Depthwise7Fn.apply(input, self.weight, self.bias)
-            if input.dtype == torch.float32 and torch.is_autocast_enabled():
-                get = getattr(torch, "get_autocast_dtype", None)
-                dt = get("cuda") if get is not None else torch.get_autocast_gpu_dtype()
-                if dt in _DTYPES:
+            if input.dtype == torch.float32:
+                dt = autocast_dtype()
+                if dt in DTYPES16:
                     return _Depthwise7Fn.apply(input.to(dt), self.weight, self.bias)
         return super().forward(input)
-
-
-def _as_depthwise7(conv: nn.Conv2d) -> DepthwiseConv7x7:
-    # the same module state under the new class: parameters (the same Parameter objects), hooks, training flag
-    new = DepthwiseConv7x7.__new__(DepthwiseConv7x7)
-    new.__dict__ = conv.__dict__.copy()
-    for k in ("_parameters", "_buffers", "_modules"):
-        new.__dict__[k] = conv.__dict__[k].copy()
-    return new
 
 
 def convert_depthwise7(model: nn.Module) -> int:
     """Swap every qualifying ``nn.Conv2d`` below ``model`` for a :class:`DepthwiseConv7x7` holding the same
     ``Parameter`` objects; returns how many were swapped (0 on a second call).  Call it before the parameters are
     flattened (``optim.flat.FlatParams``)."""
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if type(child) is nn.Conv2d and qualifies7(child):
-                setattr(parent, name, _as_depthwise7(child))
-                n += 1
-    return n
+    return swap_children(model, {nn.Conv2d: DepthwiseConv7x7}, qualifies7)

@@ -25,12 +25,11 @@ import torch
 import torch.nn as nn
 
 from . import native
+from ._module import DTYPES16, autocast_dtype, nchw, nhwc, swap_children
 from ..models.modern import LayerNorm2d
 
 # persistent blocks the kernels are given at most: four per CU (256 CUs)
 MAX_BLOCKS = 1024
-
-_DTYPES = (torch.bfloat16, torch.float16)
 
 
 def layernorm_plan(rows: int, C: int, max_blocks: int | None = None):
@@ -82,13 +81,12 @@ def qualifies(m: nn.LayerNorm) -> bool:
 
 def _native_dtype(m: nn.LayerNorm, x: torch.Tensor):
     """The autocast dtype when ``x`` (already ``[..., C]``) takes the kernels, else None."""
-    if not (x.is_cuda and torch.is_autocast_enabled() and qualifies(m) and x.dim() >= 1
+    if not (x.is_cuda and qualifies(m) and x.dim() >= 1
             and x.shape[-1] == m.normalized_shape[0] and 0 < x.numel() < 2 ** 40 and x.is_contiguous()
             and x.data_ptr() % 16 == 0 and m.weight.dtype == torch.float32):
         return None
-    get = getattr(torch, "get_autocast_dtype", None)
-    dt = get("cuda") if get is not None else torch.get_autocast_gpu_dtype()
-    return dt if dt in _DTYPES and x.dtype in (dt, torch.float32) else None
+    dt = autocast_dtype()
+    return dt if dt in DTYPES16 and x.dtype in (dt, torch.float32) else None
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -134,31 +132,15 @@ class NativeLayerNorm2d(LayerNorm2d):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() == 4:
-            xp = x.permute(0, 2, 3, 1)
+            xp = nhwc(x)
             dt = _native_dtype(self, xp)
             if dt is not None:
-                return _LayerNormFn.apply(xp, self.weight, self.bias, self.eps, dt).permute(0, 3, 1, 2)
+                return nchw(_LayerNormFn.apply(xp, self.weight, self.bias, self.eps, dt))
         return super().forward(x)
-
-
-def _as(cls, m: nn.LayerNorm):
-    # the same module state under the new class: parameters (the same Parameter objects), hooks, training flag
-    new = cls.__new__(cls)
-    new.__dict__ = m.__dict__.copy()
-    for k in ("_parameters", "_buffers", "_modules"):
-        new.__dict__[k] = m.__dict__[k].copy()
-    return new
 
 
 def convert_layernorm(model: nn.Module) -> int:
     """Swap every qualifying ``nn.LayerNorm`` / ``LayerNorm2d`` below ``model`` for its native subclass holding the
     same ``Parameter`` objects; returns how many were swapped (0 on a second call).  Call it before the parameters are
     flattened (``optim.flat.FlatParams``)."""
-    kinds = {nn.LayerNorm: NativeLayerNorm, LayerNorm2d: NativeLayerNorm2d}
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if type(child) in kinds and qualifies(child):
-                setattr(parent, name, _as(kinds[type(child)], child))
-                n += 1
-    return n
+    return swap_children(model, {nn.LayerNorm: NativeLayerNorm, LayerNorm2d: NativeLayerNorm2d}, qualifies)

@@ -21,13 +21,12 @@ import torch
 import torch.nn as nn
 
 from . import native
+from ._module import DTYPES16, grad_nhwc, nchw, nhwc, swap_children
 from .bnact import CONV_STATS_ATTR
 
 # blocks the weight gradient aims for: a few per CU (256 CUs, two 64 KiB-LDS blocks resident on each)
 WGRAD_TARGET_BLOCKS = 1024
 MIN_CH, MAX_CH = 8, 2048
-
-_DTYPES = (torch.bfloat16, torch.float16)
 
 
 def fits(M: int, C: int, K: int) -> bool:
@@ -101,23 +100,21 @@ class _PointwiseFn(torch.autograd.Function):
         K, C = weight.shape[:2]
         # the 16-bit operand of the kernels, derived from the master here (not an autograd op)
         w16 = weight.detach().reshape(K, C).to(x.dtype)
-        y = pwconv_fwd(x.permute(0, 2, 3, 1), w16)  # NHWC view of the channels_last storage: no copy
+        y = pwconv_fwd(nhwc(x), w16)
         ctx.save_for_backward(x, w16)
-        return y.permute(0, 3, 1, 2)  # channels_last NCHW view
+        return nchw(y)
 
     @staticmethod
     def backward(ctx, gy):
         x, w16 = ctx.saved_tensors
         K, C = w16.shape
-        g = gy.permute(0, 2, 3, 1)
-        if g.dtype != x.dtype or not g.is_contiguous():
-            g = g.to(x.dtype).contiguous()
+        g = grad_nhwc(gy, x.dtype)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = pwconv_dgrad(g, w16).permute(0, 3, 1, 2)  # w16^T made here: once per backward, at most 8 MiB
+            dx = nchw(pwconv_dgrad(g, w16))  # w16^T made here: once per backward, at most 8 MiB
         dw = None
         if ctx.needs_input_grad[1]:
-            dw = pwconv_wgrad(x.permute(0, 2, 3, 1), g).view(K, C, 1, 1)  # fp32 all the way
+            dw = pwconv_wgrad(nhwc(x), g).view(K, C, 1, 1)  # fp32 all the way
         return dx, dw
 
 
@@ -129,10 +126,10 @@ class _PointwiseStatsFn(torch.autograd.Function):
     def forward(ctx, x, weight):
         K, C = weight.shape[:2]
         w16 = weight.detach().reshape(K, C).to(x.dtype)
-        y, slots, _ = pwconv_fwd_stats(x.permute(0, 2, 3, 1), w16)
+        y, slots, _ = pwconv_fwd_stats(nhwc(x), w16)
         ctx.save_for_backward(x, w16)
         ctx.mark_non_differentiable(slots)
-        return y.permute(0, 3, 1, 2), slots
+        return nchw(y), slots
 
     @staticmethod
     def backward(ctx, gy, _gslots):
@@ -151,7 +148,7 @@ class PointwiseConv2d(nn.Conv2d):
     emit_stats = False
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
-        if (input.is_cuda and input.dtype in _DTYPES and input.dim() == 4 and qualifies(self)
+        if (input.is_cuda and input.dtype in DTYPES16 and input.dim() == 4 and qualifies(self)
                 and input.is_contiguous(memory_format=torch.channels_last) and input.numel() > 0
                 and input.data_ptr() % 16 == 0  # the kernels' 16-byte accesses
                 and fits(input.numel() // self.in_channels, self.in_channels, self.out_channels)):
@@ -167,23 +164,8 @@ class PointwiseConv2d(nn.Conv2d):
         return _PointwiseFn.apply(input, self.weight)
 
 
-def _as_pointwise(conv: nn.Conv2d) -> PointwiseConv2d:
-    # the same module state under the new class: parameters (the same Parameter objects), hooks, training flag
-    new = PointwiseConv2d.__new__(PointwiseConv2d)
-    new.__dict__ = conv.__dict__.copy()
-    for k in ("_parameters", "_buffers", "_modules"):
-        new.__dict__[k] = conv.__dict__[k].copy()
-    return new
-
-
 def convert_pointwise(model: nn.Module) -> int:
     """Swap every qualifying ``nn.Conv2d`` below ``model`` for a :class:`PointwiseConv2d` holding the same
     ``Parameter``; returns how many were swapped (0 on a second call).  Call it before the parameters are
     flattened (``optim.flat.FlatParams``)."""
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if type(child) is nn.Conv2d and qualifies(child):
-                setattr(parent, name, _as_pointwise(child))
-                n += 1
-    return n
+    return swap_children(model, {nn.Conv2d: PointwiseConv2d}, qualifies)

@@ -22,14 +22,13 @@ import torch
 import torch.nn as nn
 
 from . import native
+from ._module import DTYPES16, autocast_dtype, grad_nhwc, nchw, nhwc, swap_children
 
 # blocks the weight gradient aims for: the 512 that are resident at once (256 CUs, two 64 KiB-LDS blocks on each).
 # More splits cost more in wgrad_reduce, whose 864 outputs each sum the splits serially, than they gain in the kernel
 # (profiles/stem3x3_mi355x.md)
 WGRAD_TARGET_BLOCKS = 512
 MIN_K, MAX_K = 8, 64
-
-_DTYPES = (torch.bfloat16, torch.float16)
 
 
 def out_hw(H: int, W: int):
@@ -76,14 +75,6 @@ def qualifies(m: nn.Conv2d) -> bool:
             and m.out_channels % 8 == 0 and MIN_K <= m.out_channels <= MAX_K)
 
 
-def _autocast_dtype():
-    """The CUDA autocast dtype, or None when CUDA autocast is off."""
-    if not torch.is_autocast_enabled():
-        return None
-    get = getattr(torch, "get_autocast_dtype", None)
-    return get("cuda") if get is not None else torch.get_autocast_gpu_dtype()
-
-
 class _StemFn(torch.autograd.Function):
     """``x``: logical NCHW fp32, dense in channels_last, no gradient; ``weight``: the fp32 ``[K, 3, 3, 3]`` (K, C, R, S)
     master; ``dtype``: the compute dtype."""
@@ -92,21 +83,18 @@ class _StemFn(torch.autograd.Function):
     def forward(ctx, x, weight, dtype):
         # the 16-bit KRSC operand of the kernels, derived from the master here (not an autograd op)
         w16 = weight.detach().permute(0, 2, 3, 1).to(dtype).contiguous()
-        y = stem3x3_fwd(x.permute(0, 2, 3, 1), w16)  # NHWC view of the channels_last storage: no copy
+        y = stem3x3_fwd(nhwc(x), w16)
         ctx.save_for_backward(x)
         ctx.dtype = dtype
-        return y.permute(0, 3, 1, 2)  # channels_last NCHW view
+        return nchw(y)
 
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
         dw = None
         if ctx.needs_input_grad[1]:
-            g = gy.permute(0, 2, 3, 1)
-            if g.dtype != ctx.dtype or not g.is_contiguous():
-                g = g.to(ctx.dtype).contiguous()
             # fp32 all the way; KRSC -> the parameter's (K, C, R, S)
-            dw = stem3x3_wgrad(x.permute(0, 2, 3, 1), g).permute(0, 3, 1, 2)
+            dw = stem3x3_wgrad(nhwc(x), grad_nhwc(gy, ctx.dtype)).permute(0, 3, 1, 2)
         return None, dw, None
 
 
@@ -120,29 +108,14 @@ class StemConv2d(nn.Conv2d):
         if (input.is_cuda and input.dtype == torch.float32 and input.dim() == 4 and not input.requires_grad
                 and qualifies(self) and input.shape[1] == 3 and input.numel() > 0
                 and input.is_contiguous(memory_format=torch.channels_last)):
-            dtype = _autocast_dtype()
-            if dtype in _DTYPES and fits(input.shape[0], input.shape[2], input.shape[3], self.out_channels):
+            dtype = autocast_dtype()
+            if dtype in DTYPES16 and fits(input.shape[0], input.shape[2], input.shape[3], self.out_channels):
                 return _StemFn.apply(input, self.weight, dtype)
         return super().forward(input)
-
-
-def _as_stem(conv: nn.Conv2d) -> StemConv2d:
-    # the same module state under the new class: parameters (the same Parameter objects), hooks, training flag
-    new = StemConv2d.__new__(StemConv2d)
-    new.__dict__ = conv.__dict__.copy()
-    for k in ("_parameters", "_buffers", "_modules"):
-        new.__dict__[k] = conv.__dict__[k].copy()
-    return new
 
 
 def convert_stem(model: nn.Module) -> int:
     """Swap every qualifying ``nn.Conv2d`` below ``model`` for a :class:`StemConv2d` holding the same ``Parameter``;
     returns how many were swapped (0 on a second call).  Call it before the parameters are flattened
     (``optim.flat.FlatParams``)."""
-    n = 0
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if type(child) is nn.Conv2d and qualifies(child):
-                setattr(parent, name, _as_stem(child))
-                n += 1
-    return n
+    return swap_children(model, {nn.Conv2d: StemConv2d}, qualifies)

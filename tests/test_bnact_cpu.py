@@ -23,7 +23,6 @@ import torch.nn as nn
 
 import _bnact_numerics as bm
 import _numerics as nm
-from pytorch_distributed_template_amd import cli
 from pytorch_distributed_template_amd.models import registry
 from pytorch_distributed_template_amd.ops.bnact import ACTS, BNAct2d, convert_bnact, qualifies
 
@@ -148,16 +147,6 @@ def test_module_constructor_and_cpu_fallback(act, C):
     with pytest.raises(RuntimeError) as eb:
         b(torch.randn(2, 8, 3, 3))
     assert str(ea.value) == str(eb.value)
-
-
-def test_flag_parses():
-    for mode in ("dp", "ddp", "ddp_amp"):
-        p = cli.build_parser(mode)
-        assert p.parse_args([]).native_bnact == "off"
-        assert p.parse_args(["--native-bnact", "on"]).native_bnact == "on"
-        assert p.parse_args(["--native-bnact", "off"]).native_bnact == "off"
-        with pytest.raises(SystemExit):
-            p.parse_args(["--native-bnact", "auto"])
 
 
 def _losses(tmp_path, script, flag, extra=()):

@@ -18,7 +18,6 @@ import pytest
 import torch
 import torch.nn as nn
 
-from pytorch_distributed_template_amd import cli
 from pytorch_distributed_template_amd.models import registry
 from pytorch_distributed_template_amd.ops import bnact, native, pointwise
 from pytorch_distributed_template_amd.ops.bnact import BNAct2d, CONV_STATS_ATTR, convert_bnact
@@ -268,16 +267,6 @@ def test_eight_argument_apply_still_works(fake):
 
 
 # ------------------------------------------------------------------------------------------ flag and runner
-def test_flag_parses():
-    for mode in ("dp", "ddp", "ddp_amp"):
-        p = cli.build_parser(mode)
-        assert p.parse_args([]).native_convstats == "off"
-        assert p.parse_args(["--native-convstats", "on"]).native_convstats == "on"
-        assert p.parse_args(["--native-convstats", "off"]).native_convstats == "off"
-        with pytest.raises(SystemExit):
-            p.parse_args(["--native-convstats", "auto"])
-
-
 def _run(tmp_path, tag, extra):
     out = str(tmp_path / ("out_" + tag))
     args = ["dataparallel.py", "--outpath", out, "-a", "mobilenet_v2", "-b", "4", "--synthetic", "--synthetic-train-size",

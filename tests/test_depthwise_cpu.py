@@ -13,7 +13,6 @@ import pytest
 import torch
 import torch.nn as nn
 
-from pytorch_distributed_template_amd import cli
 from pytorch_distributed_template_amd.models import registry
 from pytorch_distributed_template_amd.ops.depthwise import DepthwiseConv2d, convert_depthwise, qualifies
 
@@ -87,16 +86,6 @@ def test_module_constructor_and_cpu_gradients():
     a(x).square().sum().backward()
     b(x2).square().sum().backward()
     assert torch.equal(a.weight.grad, b.weight.grad) and torch.equal(x.grad, x2.grad)
-
-
-def test_flag_parses():
-    for mode in ("dp", "ddp", "ddp_amp"):
-        p = cli.build_parser(mode)
-        assert p.parse_args([]).native_depthwise == "off"
-        assert p.parse_args(["--native-depthwise", "on"]).native_depthwise == "on"
-        assert p.parse_args(["--native-depthwise", "off"]).native_depthwise == "off"
-        with pytest.raises(SystemExit):
-            p.parse_args(["--native-depthwise", "auto"])
 
 
 def _losses(tmp_path, flag):

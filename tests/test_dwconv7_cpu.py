@@ -5,7 +5,6 @@ import pytest
 import torch
 import torch.nn as nn
 
-from pytorch_distributed_template_amd import cli
 from pytorch_distributed_template_amd.models import registry
 from pytorch_distributed_template_amd.ops.depthwise import convert_depthwise
 from pytorch_distributed_template_amd.ops.depthwise7 import DepthwiseConv7x7, convert_depthwise7, qualifies7
@@ -58,12 +57,3 @@ def test_qualifies7(kw, want):
     kw.setdefault("padding", 3)
     kw.setdefault("groups", c)
     assert qualifies7(nn.Conv2d(c, c, k, **kw)) is want
-
-
-def test_flag_parses():
-    for mode in ("dp", "ddp", "ddp_amp"):
-        p = cli.build_parser(mode)
-        assert p.parse_args([]).native_dw7 == "off"
-        assert p.parse_args(["--native-dw7", "on"]).native_dw7 == "on"
-        with pytest.raises(SystemExit):
-            p.parse_args(["--native-dw7", "auto"])

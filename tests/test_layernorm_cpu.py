@@ -7,7 +7,6 @@ import sys
 import pytest
 import torch
 
-from pytorch_distributed_template_amd import cli
 from pytorch_distributed_template_amd.models import registry
 from pytorch_distributed_template_amd.ops.layernorm import NativeLayerNorm, NativeLayerNorm2d, convert_layernorm
 
@@ -39,15 +38,6 @@ def test_conversion_keeps_state_and_results():
     with torch.no_grad():
         assert torch.equal(model(x), ref(x))  # CPU: the modules fall back to F.layer_norm
     ref.load_state_dict(model.state_dict())
-
-
-def test_flag_parses():
-    for mode in ("dp", "ddp", "ddp_amp"):
-        p = cli.build_parser(mode)
-        assert p.parse_args([]).native_layernorm == "off"
-        assert p.parse_args(["--native-layernorm", "on"]).native_layernorm == "on"
-        with pytest.raises(SystemExit):
-            p.parse_args(["--native-layernorm", "auto"])
 
 
 def test_cpu_run_logs_the_conversion(tmp_path):

@@ -22,7 +22,6 @@ import torch.nn as nn
 
 import _numerics as nm
 import _stem3x3_cases as sc
-from pytorch_distributed_template_amd import cli
 from pytorch_distributed_template_amd.models import registry
 from pytorch_distributed_template_amd.ops.stemconv import StemConv2d, convert_stem, qualifies
 
@@ -255,16 +254,6 @@ def test_module_constructor_and_cpu_gradients():
     assert torch.equal(a.weight.grad, b.weight.grad) and torch.equal(x.grad, x2.grad)
     with torch.autocast("cpu", dtype=torch.bfloat16):  # CPU autocast is not the kernels' case either
         assert torch.equal(a(x.detach()), b(x.detach()))
-
-
-def test_flag_parses():
-    for mode in ("dp", "ddp", "ddp_amp"):
-        p = cli.build_parser(mode)
-        assert p.parse_args([]).native_stem == "off"
-        assert p.parse_args(["--native-stem", "on"]).native_stem == "on"
-        assert p.parse_args(["--native-stem", "off"]).native_stem == "off"
-        with pytest.raises(SystemExit):
-            p.parse_args(["--native-stem", "auto"])
 
 
 def _losses(tmp_path, flag):

@@ -137,3 +137,55 @@ def test_two_training_steps_of_the_converted_network(arch, dt, geom, monkeypatch
         print(f"{rig.family}: {sub} of {sum(d.numel() for d in dys)} dY elements of the pointwise weight gradients are "
               "subnormal")
     print(f"{rig.family}: {time.perf_counter() - t0:.1f} s")
+
+
+def _layout_cases():
+    """(module, input, the launch its backward must make) for each converted class whose backward takes its gradient
+    through ``ops._module.grad_nhwc``, at the smallest geometry of its own module test (odd maps)."""
+    from pytorch_distributed_template_amd.ops import bnact, depthwise, depthwise7, pointwise, stemconv
+    act = lambda *s: torch.randn(s, device=DEV).contiguous(memory_format=torch.channels_last)
+    return {
+        "depthwise": lambda dt: (depthwise.DepthwiseConv2d(16, 16, 3, padding=1, groups=16, bias=False),
+                                 act(2, 16, 9, 9).to(dt).requires_grad_(True), "dwconv_wgrad"),
+        "dw7": lambda dt: (depthwise7.DepthwiseConv7x7(16, 16, 7, padding=3, groups=16, bias=True),
+                           act(2, 16, 7, 7).to(dt).requires_grad_(True), "dwconv7_wgrad"),
+        "pointwise": lambda dt: (pointwise.PointwiseConv2d(16, 24, 1, bias=False),
+                                 act(2, 16, 9, 9).to(dt).requires_grad_(True), "pwconv_wgrad"),
+        "stem": lambda dt: (stemconv.StemConv2d(3, 24, 3, stride=2, padding=1, bias=False), act(2, 3, 9, 7),
+                            "stem3x3_wgrad"),  # the fp32 image, no gradient
+        "bnact": lambda dt: (bnact.BNAct2d(16, act="relu6"), act(2, 16, 9, 9).to(dt).requires_grad_(True),
+                             "bnact_bwd_apply"),
+    }
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("op", ["depthwise", "dw7", "pointwise", "stem", "bnact"])
+def test_backward_is_the_same_for_every_layout_of_the_gradient(op, dt):
+    """A 16-bit ``channels_last`` upstream gradient (taken as it is) and the same values as an fp32 NCHW-contiguous one
+    (converted and re-laid by ``grad_nhwc``) reach the kernels as the same bytes: ``dx`` and every parameter gradient
+    are bitwise equal, and both backwards ran on the kernels."""
+    from pytorch_distributed_template_amd.ops import native
+    dtype = DT[dt]
+    torch.manual_seed(3)
+    m, x, kernel = _layout_cases()[op](dtype)
+    m = m.to(DEV).train()
+    got = []
+    for k in (0, 1):
+        with torch.autocast("cuda", dtype=dtype):
+            y = m(x)
+        if k == 0:
+            g16 = torch.randn_like(y)  # y is 16-bit channels_last: so is g16
+            assert g16.dtype == dtype and g16.is_contiguous(memory_format=torch.channels_last)
+            gy = g16
+        else:
+            gy = g16.float().contiguous()
+            assert gy.is_contiguous() and not gy.is_contiguous(memory_format=torch.channels_last)
+        before = native.C.dispatch_counts().get(kernel, 0)
+        y.backward(gy)
+        assert native.C.dispatch_counts().get(kernel, 0) - before == 1  # no fallback
+        got.append([x.grad] + [p.grad for p in m.parameters()])
+        x.grad = None
+        m.zero_grad(set_to_none=True)
+    assert got[0][0] is not None or op == "stem"
+    for a, b in zip(*got):
+        assert (a is None and b is None) or (a.dtype == b.dtype and torch.equal(a, b))

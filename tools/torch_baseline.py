@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn as nn
 from pytorch_distributed_template_amd.models import registry
+from pytorch_distributed_template_amd.ops import conversions
 
 p = argparse.ArgumentParser()
 p.add_argument("--arch", default="resnet18")
@@ -15,22 +16,7 @@ p.add_argument("--steps", type=int, default=10)
 p.add_argument("--dtype", default="bf16")
 p.add_argument("--benchmark", type=int, default=1, help="cudnn.benchmark (MIOpen search) as the reference sets it")
 p.add_argument("--cl", type=int, default=1)
-p.add_argument("--native-depthwise", default="off", choices=["off", "on"],
-               help="on: qualifying depthwise convs run on the native HIP kernels (ops/depthwise.py); off: MIOpen")
-p.add_argument("--native-bnact", default="off", choices=["off", "on"],
-               help="on: qualifying BatchNorm2d (+ ReLU / ReLU6 / Hardswish) layers run on the native fused HIP kernels "
-                    "(ops/bnact.py); off: MIOpen batch norm + a separate activation")
-p.add_argument("--native-pointwise", default="off", choices=["off", "on"],
-               help="on: qualifying 1x1 convs run on the native HIP kernels (ops/pointwise.py); off: MIOpen")
-p.add_argument("--native-stem", default="off", choices=["off", "on"],
-               help="on: a qualifying 3x3/2 first conv runs on the native HIP kernels (ops/stemconv.py); off: MIOpen")
-p.add_argument("--native-convstats", default="off", choices=["off", "on"],
-               help="on (with --native-pointwise on and --native-bnact on): converted 1x1 convs emit the statistics of "
-                    "the BatchNorm behind them (ops/convstats.py); off: the BatchNorm reads the conv output for them")
-p.add_argument("--native-dw7", default="off", choices=["off", "on"],
-               help="on: qualifying 7x7 depthwise convs run on the native HIP kernels (ops/depthwise7.py); off: MIOpen")
-p.add_argument("--native-layernorm", default="off", choices=["off", "on"],
-               help="on: qualifying LayerNorms run on the native HIP kernels (ops/layernorm.py); off: F.layer_norm")
+conversions.add_flags(p)
 a = p.parse_args()
 torch.backends.cudnn.benchmark = bool(a.benchmark)
 import threading
@@ -45,44 +31,8 @@ def _heartbeat():  # MIOpen's search can stay silent for minutes: keep the run v
 threading.Thread(target=_heartbeat, daemon=True).start()
 dev = torch.device("cuda:0")
 m = registry.create(a.arch).to(dev)
-n_dw = 0
-if a.native_depthwise == "on":
-    from pytorch_distributed_template_amd.ops.depthwise import convert_depthwise
-    n_dw = convert_depthwise(m)
-    print(f"native depthwise: {n_dw} conv(s) converted", flush=True)
-n_pw = 0
-if a.native_pointwise == "on":
-    from pytorch_distributed_template_amd.ops.pointwise import convert_pointwise
-    n_pw = convert_pointwise(m)
-    print(f"native pointwise: {n_pw} conv(s) converted", flush=True)
-n_stem = 0
-if a.native_stem == "on":
-    from pytorch_distributed_template_amd.ops.stemconv import convert_stem
-    n_stem = convert_stem(m)
-    print(f"native stem: {n_stem} conv(s) converted", flush=True)
-n_dw7 = 0
-if a.native_dw7 == "on":
-    from pytorch_distributed_template_amd.ops.depthwise7 import convert_depthwise7
-    n_dw7 = convert_depthwise7(m)
-    print(f"native dw7: {n_dw7} conv(s) converted", flush=True)
-n_ln = 0
-if a.native_layernorm == "on":
-    from pytorch_distributed_template_amd.ops.layernorm import convert_layernorm
-    n_ln = convert_layernorm(m)
-    print(f"native layernorm: {n_ln} LayerNorm(s) converted", flush=True)
-n_bn = n_act = 0
-if a.native_bnact == "on":
-    from pytorch_distributed_template_amd.ops.bnact import convert_bnact
-    n_bn, n_act = convert_bnact(m)
-    print(f"native bnact: {n_bn} BatchNorm(s) converted, {n_act} activation(s) fused", flush=True)
-n_cs = 0
-if a.native_convstats == "on":
-    if a.native_pointwise != "on" or a.native_bnact != "on":
-        print("native convstats: ignored, it needs --native-pointwise on and --native-bnact on", flush=True)
-    else:
-        from pytorch_distributed_template_amd.ops.convstats import convert_convstats
-        n_cs = convert_convstats(m)
-        print(f"native convstats: {n_cs} conv/BatchNorm pair(s) fused", flush=True)
+# the runner's conversions (the tool never converts to SyncBatchNorm)
+counts = conversions.apply(m, a, a.arch, False, lambda s: print(s, flush=True))
 if a.cl:
     m = m.to(memory_format=torch.channels_last)
 opt = torch.optim.SGD(m.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4)
@@ -111,12 +61,11 @@ for _ in range(a.steps):
     print(".", end="", flush=True)
 print()
 el = (time.time() - t) / a.steps
-print(json.dumps({"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl,
-                  "native_depthwise": a.native_depthwise, "depthwise_converted": n_dw,
-                  "native_pointwise": a.native_pointwise, "pointwise_converted": n_pw,
-                  "native_stem": a.native_stem, "stem_converted": n_stem,
-                  "native_dw7": a.native_dw7, "dw7_converted": n_dw7,
-                  "native_layernorm": a.native_layernorm, "layernorm_converted": n_ln,
-                  "native_bnact": a.native_bnact, "bnact_converted": n_bn, "bnact_fused": n_act,
-                  "native_convstats": a.native_convstats, "convstats_pairs": n_cs, "ms_per_step": el * 1e3,
-                  "img_per_s": a.bs / el, "max_mem_GB": torch.cuda.max_memory_allocated() / 1e9}))
+rec = {"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl}
+for c in conversions.TABLE:  # the flag as given and what it converted, 0 where it did not run
+    keys = {"bnact": ("bnact_converted", "bnact_fused"), "convstats": ("convstats_pairs",)}.get(
+        c.name, (c.name + "_converted",))
+    rec["native_" + c.name] = getattr(a, "native_" + c.name)
+    rec.update(zip(keys, counts.get(c.name, (0, 0))))
+rec.update(ms_per_step=el * 1e3, img_per_s=a.bs / el, max_mem_GB=torch.cuda.max_memory_allocated() / 1e9)
+print(json.dumps(rec))
