@@ -31,6 +31,7 @@
 #include "kernels/dwconv7.h"
 #include "kernels/fp32.h"
 #include "kernels/layernorm.h"
+#include "kernels/winattn.h"
 #include "kernels/loss.h"
 #include "kernels/optim.h"
 #include "kernels/pool.h"
@@ -1083,6 +1084,120 @@ int64_t layernorm_bwd(const Tensor& dy, const Tensor& x, const Tensor& mean, con
   return pp ? p.blocks : 0;
 }
 
+// ------------------------------------------------------- window attention (winattn.hip)
+// q / k / v / dy and the gradients: 16-bit views [Bw][N][heads][32] with any strides that are multiples of 8 and a
+// dense last dimension (the three slices of a packed qkv [Bw][N][3][heads][32] are such views); y dense
+// [Bw][N][heads][32]; bias fp32 [heads][N][N]; region uint8 [nwin][N]; stat fp32 [Bw][heads][N][2]; the caller allocates
+bool winattn_fits(int64_t Bw, int64_t heads, int64_t N, int64_t head_dim) {
+  return pdt::winattn_fits(Bw, heads, N, head_dim);
+}
+
+pdt::WaPlan wa_plan(const char* op, int64_t Bw, int64_t heads, int64_t N, int64_t max_blocks) {
+  TORCH_CHECK(pdt::winattn_fits(Bw, heads, N, 32), op, ": outside the contract (1 <= N <= 64, head dimension 32): Bw = ",
+              Bw, ", heads = ", heads, ", N = ", N);
+  TORCH_CHECK(max_blocks >= 1 && max_blocks < (int64_t(1) << 30), op, ": bad max_blocks");
+  return pdt::winattn_plan(Bw, (int)heads, (int)max_blocks);
+}
+
+// (blocks, slabs): persistent blocks and dbias partial slabs [slabs][heads][N][N] of the backward
+std::vector<int64_t> winattn_plan(int64_t Bw, int64_t heads, int64_t N, int64_t max_blocks) {
+  const pdt::WaPlan p = wa_plan("winattn_plan", Bw, heads, N, max_blocks);
+  return {p.blocks, p.slabs};
+}
+
+// `out`: the kernel writes it, so every dimension longer than 1 needs a positive stride and no two elements may share
+// an address; the stride of a dimension of size 1 is never used and may be anything
+pdt::WaOperand wa_operand(const char* op, const Tensor& t, const char* name, int dt, int64_t Bw, int64_t N,
+                          int64_t heads, bool out = false) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(0) == Bw && t.size(1) == N && t.size(2) == heads && t.size(3) == 32,
+              op, ": ", name, " must be a GPU view [Bw][N][heads][32]");
+  const int have = t.scalar_type() == at::kBFloat16 ? pdt::kBF16 : t.scalar_type() == at::kHalf ? pdt::kF16 : -1;
+  TORCH_CHECK(have == dt, op, ": ", name, " must have the 16-bit dtype of q");
+  TORCH_CHECK(t.stride(3) == 1 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name,
+              " needs a dense last dimension and 16-byte alignment");
+  int64_t st[3];
+  for (int d = 0; d < 3; ++d) {
+    st[d] = t.size(d) > 1 ? t.stride(d) : 0;
+    TORCH_CHECK(st[d] % 8 == 0 && st[d] >= 0 && !(out && t.size(d) > 1 && st[d] == 0), op, ": ", name,
+                " needs strides that are multiples of 8", out ? " and positive" : " and not negative");
+  }
+  if (out) {  // sorted by stride, every dimension must step over the whole extent of the ones below it
+    int64_t ext = 32;
+    int order[3] = {0, 1, 2};
+    std::sort(order, order + 3, [&](int a, int b) { return st[a] < st[b]; });
+    for (int d : order) {
+      if (t.size(d) == 1) continue;
+      TORCH_CHECK(st[d] >= ext, op, ": ", name, " overlaps itself");
+      ext = st[d] * t.size(d);
+    }
+  }
+  return pdt::WaOperand{reinterpret_cast<uint16_t*>(t.data_ptr()), st[0], st[1], st[2]};
+}
+
+int wa_common(const char* op, pdt::WaArgs& a, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& bias,
+              const OptT& region, const Tensor& stat, double scale) {
+  TORCH_CHECK(q.dim() == 4, op, ": q must be [Bw][N][heads][32]");
+  const int64_t Bw = q.size(0), N = q.size(1), heads = q.size(2);
+  TORCH_CHECK(pdt::winattn_fits(Bw, heads, N, q.size(3)), op, ": outside the contract (1 <= N <= 64, head dimension 32): Bw = ",
+              Bw, ", heads = ", heads, ", N = ", N);
+  const int dt = q.scalar_type() == at::kBFloat16 ? pdt::kBF16 : pdt::kF16;
+  a.q = wa_operand(op, q, "q", dt, Bw, N, heads);
+  a.k = wa_operand(op, k, "k", dt, Bw, N, heads);
+  a.v = wa_operand(op, v, "v", dt, Bw, N, heads);
+  TORCH_CHECK(bias.numel() == heads * N * N, op, ": bias must be [heads][N][N]");
+  a.bias = pf(bias, "bias");
+  a.region = nullptr;
+  a.nwin = 0;
+  if (region.has_value()) {
+    check_dev(*region, "region");
+    TORCH_CHECK(region->scalar_type() == at::kByte && region->dim() == 2 && region->size(1) == N && region->size(0) >= 1,
+                op, ": region must be uint8 [nwin][N]");
+    a.region = region->data_ptr<uint8_t>();
+    a.nwin = (int)region->size(0);
+  }
+  TORCH_CHECK(stat.numel() == Bw * heads * N * 2, op, ": stat must be [Bw][heads][N][2]");
+  a.stat = pf(stat, "stat");
+  a.Bw = (int)Bw;
+  a.heads = (int)heads;
+  a.N = (int)N;
+  a.scale = (float)scale;
+  return dt;
+}
+
+void winattn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& bias, const OptT& region, Tensor& y,
+                 Tensor& stat, double scale, int64_t max_blocks) {
+  const char* op = "winattn_fwd";
+  pdt::WaArgs a{};
+  const int dt = wa_common(op, a, q, k, v, bias, region, stat, scale);
+  const pdt::WaPlan p = wa_plan(op, a.Bw, a.heads, a.N, max_blocks);
+  TORCH_CHECK(dt16(y, "y") == dt && y.numel() == (int64_t)a.Bw * a.N * a.heads * 32 &&
+                  reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0, op, ": y must be dense [Bw][N][heads * 32]");
+  a.y = p16(y, "y");
+  pdt::winattn_fwd_launch(dt, a, p, cur_stream());
+  launched(op);
+}
+
+// dq / dk / dv with their own strides, and the dbias partial slabs [slabs][heads][N][N] for the plan of `max_blocks`;
+// returns the number of slabs written, to be summed with wgrad_reduce
+int64_t winattn_bwd(const Tensor& dy, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& bias,
+                    const OptT& region, const Tensor& stat, Tensor& dq, Tensor& dk, Tensor& dv, Tensor& partial,
+                    double scale, int64_t max_blocks) {
+  const char* op = "winattn_bwd";
+  pdt::WaArgs a{};
+  const int dt = wa_common(op, a, q, k, v, bias, region, stat, scale);
+  const pdt::WaPlan p = wa_plan(op, a.Bw, a.heads, a.N, max_blocks);
+  a.dy = wa_operand(op, dy, "dy", dt, a.Bw, a.N, a.heads);
+  a.dq = wa_operand(op, dq, "dq", dt, a.Bw, a.N, a.heads, true);
+  a.dk = wa_operand(op, dk, "dk", dt, a.Bw, a.N, a.heads, true);
+  a.dv = wa_operand(op, dv, "dv", dt, a.Bw, a.N, a.heads, true);
+  TORCH_CHECK(partial.numel() >= (int64_t)p.slabs * a.heads * a.N * a.N, op, ": partial holds ", partial.numel(),
+              " floats, the plan needs ", (int64_t)p.slabs * a.heads * a.N * a.N);
+  a.partial = pf(partial, "partial");
+  pdt::winattn_bwd_launch(dt, a, p, cur_stream());
+  launched(op);
+  return p.slabs;
+}
+
 // ------------------------------------------------------- pointwise (1x1) convolution (pwconv.hip)
 // 1x1, stride 1, pad 0, groups 1, no bias; x / y / dy / dx NHWC 16-bit seen as [M][channels], w [K][C] 16-bit
 // (the backward data takes w^T as a [C][K] tensor).  C % 8 == K % 8 == 0, 8 <= C, K <= 2048.
@@ -1910,6 +2025,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rstd"), py::arg("rows"), py::arg("C"), py::arg("eps"), py::arg("max_blocks"));
   m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"), py::arg("mean"), py::arg("rstd"),
         py::arg("gamma"), py::arg("dx"), py::arg("partials"), py::arg("rows"), py::arg("C"), py::arg("max_blocks"));
+  m.def("winattn_fits", &winattn_fits, py::arg("Bw"), py::arg("heads"), py::arg("N"), py::arg("head_dim"));
+  m.def("winattn_plan", &winattn_plan, py::arg("Bw"), py::arg("heads"), py::arg("N"), py::arg("max_blocks"));
+  m.def("winattn_fwd", &winattn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"), py::arg("region"),
+        py::arg("y"), py::arg("stat"), py::arg("scale"), py::arg("max_blocks"));
+  m.def("winattn_bwd", &winattn_bwd, py::arg("dy"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"),
+        py::arg("region"), py::arg("stat"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("partial"),
+        py::arg("scale"), py::arg("max_blocks"));
   m.def("pwconv_fits", &pwconv_fits, py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd_stats", &pwconv_fwd_stats, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("slots"), py::arg("M"),

@@ -1,5 +1,6 @@
-"""The torch engine's opt-in native ops as one table: which ``--native-<name>`` flags exist, the order their conversions
-run in, what each needs and what it reports.  ``cli.py``, ``engine/runner.py`` and ``tools/torch_baseline.py`` all read
+"""The torch engine's opt-in native ops as two tuples of records, ``TABLE`` (convolutions and normalisations) and, run
+after it, ``ATTENTION``: which ``--native-<name>`` flags exist, the order their conversions run in, what each needs and
+what it reports.  ``cli.py``, ``engine/runner.py`` and ``tools/torch_baseline.py`` all read
 it, so they convert a model the same way.  A new op is one module under ``ops/`` plus one record here."""
 from __future__ import annotations
 
@@ -74,23 +75,35 @@ TABLE = (
 )
 
 
+# the ops beyond the convolution / normalisation family, run after TABLE in this order
+ATTENTION = (
+    Conversion(
+        "winattn",
+        "torch engine: run the window attention of Swin, Swin V2 and MaxViT blocks (head dimension 32, at most 64 "
+        "tokens per window, no active attention dropout) on the native HIP kernels where the qkv is a 16-bit GPU "
+        "tensor; the relative-position bias stays fp32 and the shift mask is a label table; elsewhere (CPU, fp32, "
+        "validation) the modules fall back to F.scaled_dot_product_attention",
+        "winattn", "convert_window_attention", "{0} attention module(s) of {arch} converted"),
+)
+
+
 def add_flags(parser) -> None:
     """One ``--native-<name> {off,on}`` flag (default off) per record on ``parser`` (or an argument group)."""
-    for c in TABLE:
+    for c in TABLE + ATTENTION:
         parser.add_argument("--native-" + c.name, default="off", choices=["off", "on"], help=c.help)
 
 
 def apply(model, flags, arch: str, syncbn_converts: bool, say) -> dict:
-    """Run on ``model``, in table order, every conversion whose ``flags.native_<name>`` is ``"on"`` (a missing attribute
-    is off) and report each through ``say(line)``: what it converted, or why it is ignored (a missing prerequisite
-    first, then ``syncbn_converts``: the caller will turn the BatchNorms into SyncBatchNorm).  Returns
+    """Run on ``model``, in table order (``TABLE``, then ``ATTENTION``), every conversion whose ``flags.native_<name>``
+    is ``"on"`` (a missing attribute is off) and report each through ``say(line)``: what it converted, or why it is
+    ignored (a missing prerequisite first, then ``syncbn_converts``: the caller will turn the BatchNorms into SyncBatchNorm).  Returns
     ``{name: tuple of counts}`` of the conversions that ran.  Call it before the parameters are flattened: the converted
     modules keep the same ``Parameter`` objects."""
     def on(name):
         return getattr(flags, "native_" + name, "off") == "on"
 
     counts = {}
-    for c in TABLE:
+    for c in TABLE + ATTENTION:
         if not on(c.name):
             continue
         if not all(on(n) for n in c.needs):

@@ -62,7 +62,7 @@ for _ in range(a.steps):
 print()
 el = (time.time() - t) / a.steps
 rec = {"arch": a.arch, "bs": a.bs, "dtype": a.dtype, "channels_last": a.cl}
-for c in conversions.TABLE:  # the flag as given and what it converted, 0 where it did not run
+for c in conversions.TABLE + conversions.ATTENTION:  # the flag as given and what it converted, 0 where it did not run
     keys = {"bnact": ("bnact_converted", "bnact_fused"), "convstats": ("convstats_pairs",)}.get(
         c.name, (c.name + "_converted",))
     rec["native_" + c.name] = getattr(a, "native_" + c.name)
