@@ -32,6 +32,7 @@
 #include "kernels/fp32.h"
 #include "kernels/layernorm.h"
 #include "kernels/winattn.h"
+#include "kernels/mha.h"
 #include "kernels/loss.h"
 #include "kernels/optim.h"
 #include "kernels/pool.h"
@@ -1108,9 +1109,9 @@ std::vector<int64_t> winattn_plan(int64_t Bw, int64_t heads, int64_t N, int64_t 
 // `out`: the kernel writes it, so every dimension longer than 1 needs a positive stride and no two elements may share
 // an address; the stride of a dimension of size 1 is never used and may be anything
 pdt::WaOperand wa_operand(const char* op, const Tensor& t, const char* name, int dt, int64_t Bw, int64_t N,
-                          int64_t heads, bool out = false) {
-  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(0) == Bw && t.size(1) == N && t.size(2) == heads && t.size(3) == 32,
-              op, ": ", name, " must be a GPU view [Bw][N][heads][32]");
+                          int64_t heads, bool out = false, int64_t hd = 32) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(0) == Bw && t.size(1) == N && t.size(2) == heads && t.size(3) == hd,
+              op, ": ", name, " must be a GPU view [Bw][N][heads][", hd, "]");
   const int have = t.scalar_type() == at::kBFloat16 ? pdt::kBF16 : t.scalar_type() == at::kHalf ? pdt::kF16 : -1;
   TORCH_CHECK(have == dt, op, ": ", name, " must have the 16-bit dtype of q");
   TORCH_CHECK(t.stride(3) == 1 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name,
@@ -1122,7 +1123,7 @@ pdt::WaOperand wa_operand(const char* op, const Tensor& t, const char* name, int
                 " needs strides that are multiples of 8", out ? " and positive" : " and not negative");
   }
   if (out) {  // sorted by stride, every dimension must step over the whole extent of the ones below it
-    int64_t ext = 32;
+    int64_t ext = hd;
     int order[3] = {0, 1, 2};
     std::sort(order, order + 3, [&](int a, int b) { return st[a] < st[b]; });
     for (int d : order) {
@@ -1196,6 +1197,58 @@ int64_t winattn_bwd(const Tensor& dy, const Tensor& q, const Tensor& k, const Te
   pdt::winattn_bwd_launch(dt, a, p, cur_stream());
   launched(op);
   return p.slabs;
+}
+
+// ------------------------------------------------------- global attention (mha.hip)
+// q / k / v / dy and the gradients: 16-bit views [B][N][heads][64] under wa_operand's rules (the three slices of a
+// packed in_proj output [B][N][3][heads][64] are such views); y dense [B][N][heads * 64]; lse and delta fp32
+// [B][heads][N] (lse in the base-2 domain); the caller allocates
+bool mha_fits(int64_t B, int64_t heads, int64_t N, int64_t head_dim) { return pdt::mha_fits(B, heads, N, head_dim); }
+
+int mha_common(const char* op, pdt::MhaArgs& a, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& y,
+               const Tensor& lse, double scale) {
+  TORCH_CHECK(q.dim() == 4, op, ": q must be [B][N][heads][64]");
+  const int64_t B = q.size(0), N = q.size(1), heads = q.size(2);
+  TORCH_CHECK(pdt::mha_fits(B, heads, N, q.size(3)), op,
+              ": outside the contract (1 <= N <= 4096, head dimension 64): B = ", B, ", heads = ", heads, ", N = ", N);
+  const int dt = q.scalar_type() == at::kBFloat16 ? pdt::kBF16 : pdt::kF16;
+  a.q = wa_operand(op, q, "q", dt, B, N, heads, false, 64);
+  a.k = wa_operand(op, k, "k", dt, B, N, heads, false, 64);
+  a.v = wa_operand(op, v, "v", dt, B, N, heads, false, 64);
+  TORCH_CHECK(dt16(y, "y") == dt && y.numel() == B * N * heads * 64 && reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0,
+              op, ": y must be dense [B][N][heads * 64]");
+  a.y = p16(y, "y");
+  TORCH_CHECK(lse.numel() == B * heads * N, op, ": lse must be [B][heads][N]");
+  a.lse = pf(lse, "lse");
+  a.B = (int)B;
+  a.heads = (int)heads;
+  a.N = (int)N;
+  a.scale = (float)scale;
+  return dt;
+}
+
+void mha_fwd(const Tensor& q, const Tensor& k, const Tensor& v, Tensor& y, Tensor& lse, double scale) {
+  const char* op = "mha_fwd";
+  pdt::MhaArgs a{};
+  const int dt = mha_common(op, a, q, k, v, y, lse, scale);
+  pdt::mha_fwd_launch(dt, a, cur_stream());
+  launched(op);
+}
+
+// dq / dk / dv with their own strides; delta: the fp32 workspace [B][heads][N] the first kernel writes
+void mha_bwd(const Tensor& dy, const Tensor& y, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& lse,
+             Tensor& dq, Tensor& dk, Tensor& dv, Tensor& delta, double scale) {
+  const char* op = "mha_bwd";
+  pdt::MhaArgs a{};
+  const int dt = mha_common(op, a, q, k, v, y, lse, scale);
+  a.dy = wa_operand(op, dy, "dy", dt, a.B, a.N, a.heads, false, 64);
+  a.dq = wa_operand(op, dq, "dq", dt, a.B, a.N, a.heads, true, 64);
+  a.dk = wa_operand(op, dk, "dk", dt, a.B, a.N, a.heads, true, 64);
+  a.dv = wa_operand(op, dv, "dv", dt, a.B, a.N, a.heads, true, 64);
+  TORCH_CHECK(delta.numel() == (int64_t)a.B * a.heads * a.N, op, ": delta must be [B][heads][N]");
+  a.delta = pf(delta, "delta");
+  pdt::mha_bwd_launch(dt, a, cur_stream());
+  launched(op);
 }
 
 // ------------------------------------------------------- pointwise (1x1) convolution (pwconv.hip)
@@ -2032,6 +2085,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("winattn_bwd", &winattn_bwd, py::arg("dy"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"),
         py::arg("region"), py::arg("stat"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("partial"),
         py::arg("scale"), py::arg("max_blocks"));
+  m.def("mha_fits", &mha_fits, py::arg("B"), py::arg("heads"), py::arg("N"), py::arg("head_dim"));
+  m.def("mha_fwd", &mha_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("y"), py::arg("lse"), py::arg("scale"));
+  m.def("mha_bwd", &mha_bwd, py::arg("dy"), py::arg("y"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("lse"),
+        py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("delta"), py::arg("scale"));
   m.def("pwconv_fits", &pwconv_fits, py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd_stats", &pwconv_fwd_stats, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("slots"), py::arg("M"),

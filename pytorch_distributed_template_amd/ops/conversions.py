@@ -84,6 +84,13 @@ ATTENTION = (
         "tensor; the relative-position bias stays fp32 and the shift mask is a label table; elsewhere (CPU, fp32, "
         "validation) the modules fall back to F.scaled_dot_product_attention",
         "winattn", "convert_window_attention", "{0} attention module(s) of {arch} converted"),
+    Conversion(
+        "mha",
+        "torch engine: run the global self-attention of ViT blocks (nn.MultiheadAttention, batch first, head "
+        "dimension 64, at most 4096 tokens, no mask, no attention weights, no active attention dropout) on the native "
+        "HIP kernels where the in-projection comes out as a 16-bit GPU tensor; elsewhere (CPU, fp32, masks, "
+        "need_weights) the modules fall back to nn.MultiheadAttention's own forward",
+        "mha", "convert_mha", "{0} attention module(s) of {arch} converted"),
 )
 
 
