@@ -33,6 +33,7 @@
 #include "kernels/layernorm.h"
 #include "kernels/winattn.h"
 #include "kernels/mha.h"
+#include "kernels/se.h"
 #include "kernels/loss.h"
 #include "kernels/optim.h"
 #include "kernels/pool.h"
@@ -1251,6 +1252,124 @@ void mha_bwd(const Tensor& dy, const Tensor& y, const Tensor& q, const Tensor& k
   launched(op);
 }
 
+// ------------------------------------------------------- squeeze-and-excitation (se.hip)
+// x / y / dy / dx: dense 16-bit NHWC [N][H][W][C] (or [N][HW][C]); w1 [S][C], b1 [S], w2 [C][S], b2 [C] and every
+// per-image vector fp32; act 0 relu / 1 silu, gate 0 sigmoid / 1 hardsigmoid; the caller allocates
+bool se_fits(int64_t N, int64_t HW, int64_t C, int64_t S) { return pdt::se_fits(N, HW, C, S); }
+
+pdt::SePlan se_plan_checked(const char* op, int64_t N, int64_t HW, int64_t C, int64_t max_blocks) {
+  TORCH_CHECK(pdt::se_fits(N, HW, C, 1), op, ": outside the contract (C % 8 == 0, 8 <= C <= 4096, N * HW * C < 2^40): N = ",
+              N, ", HW = ", HW, ", C = ", C);
+  TORCH_CHECK(max_blocks >= 1 && max_blocks < (int64_t(1) << 30), op, ": bad max_blocks");
+  return pdt::se_plan(N, HW, (int)C, (int)max_blocks);
+}
+
+// (chunks, rows_per_chunk): how the two reductions split the HW rows of an image
+std::vector<int64_t> se_plan(int64_t N, int64_t HW, int64_t C, int64_t max_blocks) {
+  const pdt::SePlan p = se_plan_checked("se_plan", N, HW, C, max_blocks);
+  return {p.chunks, p.rows_per_chunk};
+}
+
+struct SeShape {
+  int dt;
+  int64_t N, HW, C, S;
+};
+
+// shape and dtype from the activation `x` and w1; checks the four parameters that are given
+SeShape se_shape(const char* op, const Tensor& x, const Tensor& w1, const Tensor* b1, const Tensor& w2, const Tensor* b2,
+                 int64_t act, int64_t gate) {
+  SeShape g{};
+  g.dt = dt16(x, "x");
+  TORCH_CHECK(x.dim() == 3 || x.dim() == 4, op, ": x must be a dense [N][H][W][C] or [N][HW][C] tensor");
+  TORCH_CHECK(x.numel() > 0, op, ": empty x");
+  g.N = x.size(0);
+  g.C = x.size(-1);
+  g.HW = x.numel() / (g.N * g.C);
+  TORCH_CHECK(w1.dim() >= 2 && w1.size(1) == g.C && w1.numel() == w1.size(0) * g.C, op, ": w1 must be [S][C]");
+  g.S = w1.size(0);
+  TORCH_CHECK(pdt::se_fits(g.N, g.HW, g.C, g.S), op, ": outside the contract (C % 8 == 0, 8 <= C <= 4096, 1 <= S <= "
+              "512, N * HW * C < 2^40): N = ", g.N, ", HW = ", g.HW, ", C = ", g.C, ", S = ", g.S);
+  TORCH_CHECK(w2.numel() == g.C * g.S && w2.size(0) == g.C, op, ": w2 must be [C][S]");
+  TORCH_CHECK(!b1 || b1->numel() == g.S, op, ": b1 must be [S]");
+  TORCH_CHECK(!b2 || b2->numel() == g.C, op, ": b2 must be [C]");
+  TORCH_CHECK((act == pdt::kSeRelu || act == pdt::kSeSilu) && (gate == pdt::kSeSigmoid || gate == pdt::kSeHardsigmoid),
+              op, ": act must be 0 (relu) or 1 (silu), gate 0 (sigmoid) or 1 (hardsigmoid)");
+  return g;
+}
+
+uint16_t* se_act16(const char* op, const Tensor& t, const char* name, const SeShape& g) {
+  TORCH_CHECK(dt16(t, name) == g.dt && t.numel() == g.N * g.HW * g.C, op, ": ", name, " must have the dtype and size of x");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
+  return p16(t, name);
+}
+
+float* se_vec(const char* op, const Tensor& t, const char* name, int64_t n) {
+  TORCH_CHECK(t.numel() >= n, op, ": ", name, " must hold ", n, " floats, holds ", t.numel());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
+  return pf(t, name);
+}
+
+// se_pool, se_gate, se_scale: y = round(x * s) and the saved z[N][C], u[N][S], s[N][C]; partial: the workspace
+// [N][chunks][C] of the plan for `max_blocks`
+void se_fwd(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, Tensor& y, Tensor& z,
+            Tensor& u, Tensor& s, Tensor& partial, int64_t act, int64_t gate, int64_t max_blocks) {
+  const char* op = "se_fwd";
+  const SeShape g = se_shape(op, x, w1, &b1, w2, &b2, act, gate);
+  const pdt::SePlan p = se_plan_checked(op, g.N, g.HW, g.C, max_blocks);
+  const uint16_t* xp = se_act16(op, x, "x", g);
+  uint16_t* yp = se_act16(op, y, "y", g);
+  float* pp = se_vec(op, partial, "partial", g.N * p.chunks * g.C);
+  float* zp = se_vec(op, z, "z", g.N * g.C);
+  float* up = se_vec(op, u, "u", g.N * g.S);
+  float* sp = se_vec(op, s, "s", g.N * g.C);
+  hipStream_t st = cur_stream();
+  pdt::se_pool_launch(g.dt, xp, pp, g.N, g.HW, (int)g.C, p, st);
+  launched("se_pool");
+  pdt::se_gate_launch((int)act, (int)gate, pp, pf(w1, "w1"), pf(b1, "b1"), pf(w2, "w2"), pf(b2, "b2"), zp, up, sp, g.N,
+                      g.HW, (int)g.C, (int)g.S, p.chunks, st);
+  launched("se_gate");
+  pdt::se_scale_launch(g.dt, xp, sp, yp, g.N, g.HW, (int)g.C, (int)max_blocks, st);
+  launched("se_scale");
+}
+
+// se_bwd_reduce, se_gate_bwd, then se_wgrad when the four parameter gradients are given and se_bwd_apply when dx is:
+// dx = round(dy * s + g).  partial as in se_fwd; dv[N][C], du[N][S], g[N][C]: fp32 workspaces
+void se_bwd(const Tensor& dy, const Tensor& x, const Tensor& w1, const Tensor& w2, const Tensor& z, const Tensor& u,
+            const Tensor& s, const OptT& dx, const OptT& dw1, const OptT& db1, const OptT& dw2, const OptT& db2,
+            Tensor& partial, Tensor& dv, Tensor& du, Tensor& g, int64_t act, int64_t gate, int64_t max_blocks) {
+  const char* op = "se_bwd";
+  const SeShape sh = se_shape(op, x, w1, nullptr, w2, nullptr, act, gate);
+  const pdt::SePlan p = se_plan_checked(op, sh.N, sh.HW, sh.C, max_blocks);
+  const int64_t N = sh.N, C = sh.C, S = sh.S;
+  const uint16_t* xp = se_act16(op, x, "x", sh);
+  const uint16_t* dyp = se_act16(op, dy, "dy", sh);
+  const bool params = dw1.has_value();
+  TORCH_CHECK(db1.has_value() == params && dw2.has_value() == params && db2.has_value() == params, op,
+              ": the four parameter gradients come together");
+  float* pp = se_vec(op, partial, "partial", N * p.chunks * C);
+  float* zp = se_vec(op, z, "z", N * C);
+  float* up = se_vec(op, u, "u", N * S);
+  float* sp = se_vec(op, s, "s", N * C);
+  float* dvp = se_vec(op, dv, "dv", N * C);
+  float* dup = se_vec(op, du, "du", N * S);
+  float* gp = se_vec(op, g, "g", N * C);
+  hipStream_t st = cur_stream();
+  pdt::se_bwd_reduce_launch(sh.dt, dyp, xp, pp, N, sh.HW, (int)C, p, st);
+  launched("se_bwd_reduce");
+  pdt::se_gate_bwd_launch((int)act, (int)gate, pp, pf(w1, "w1"), pf(w2, "w2"), up, sp, dvp, dup, gp, N, sh.HW, (int)C,
+                          (int)S, p.chunks, st);
+  launched("se_gate_bwd");
+  if (params) {
+    pdt::se_wgrad_launch((int)act, dvp, dup, zp, up, se_vec(op, *dw1, "dw1", S * C), se_vec(op, *db1, "db1", S),
+                         se_vec(op, *dw2, "dw2", C * S), se_vec(op, *db2, "db2", C), N, (int)C, (int)S, st);
+    launched("se_wgrad");
+  }
+  if (dx.has_value()) {
+    pdt::se_bwd_apply_launch(sh.dt, dyp, sp, gp, se_act16(op, *dx, "dx", sh), N, sh.HW, (int)C, (int)max_blocks, st);
+    launched("se_bwd_apply");
+  }
+}
+
 // ------------------------------------------------------- pointwise (1x1) convolution (pwconv.hip)
 // 1x1, stride 1, pad 0, groups 1, no bias; x / y / dy / dx NHWC 16-bit seen as [M][channels], w [K][C] 16-bit
 // (the backward data takes w^T as a [C][K] tensor).  C % 8 == K % 8 == 0, 8 <= C, K <= 2048.
@@ -2089,6 +2208,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mha_fwd", &mha_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("y"), py::arg("lse"), py::arg("scale"));
   m.def("mha_bwd", &mha_bwd, py::arg("dy"), py::arg("y"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("lse"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("delta"), py::arg("scale"));
+  m.def("se_fits", &se_fits, py::arg("N"), py::arg("HW"), py::arg("C"), py::arg("S"));
+  m.def("se_plan", &se_plan, py::arg("N"), py::arg("HW"), py::arg("C"), py::arg("max_blocks"));
+  m.def("se_fwd", &se_fwd, py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("y"),
+        py::arg("z"), py::arg("u"), py::arg("s"), py::arg("partial"), py::arg("act"), py::arg("gate"),
+        py::arg("max_blocks"));
+  m.def("se_bwd", &se_bwd, py::arg("dy"), py::arg("x"), py::arg("w1"), py::arg("w2"), py::arg("z"), py::arg("u"),
+        py::arg("s"), py::arg("dx"), py::arg("dw1"), py::arg("db1"), py::arg("dw2"), py::arg("db2"), py::arg("partial"),
+        py::arg("dv"), py::arg("du"), py::arg("g"), py::arg("act"), py::arg("gate"), py::arg("max_blocks"));
   m.def("pwconv_fits", &pwconv_fits, py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("M"), py::arg("C"), py::arg("K"));
   m.def("pwconv_fwd_stats", &pwconv_fwd_stats, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("slots"), py::arg("M"),

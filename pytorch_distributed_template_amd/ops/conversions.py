@@ -91,6 +91,14 @@ ATTENTION = (
         "HIP kernels where the in-projection comes out as a 16-bit GPU tensor; elsewhere (CPU, fp32, masks, "
         "need_weights) the modules fall back to nn.MultiheadAttention's own forward",
         "mha", "convert_mha", "{0} attention module(s) of {arch} converted"),
+    Conversion(
+        "se",
+        "torch engine: run the squeeze-and-excitation blocks of EfficientNet / V2, MobileNetV3, RegNet-Y and MaxViT "
+        "(ReLU or SiLU squeeze, Sigmoid or Hardsigmoid gate, biased 1x1 fc1 / fc2, channels %% 8 == 0 and within "
+        "8..4096, squeeze width <= 512) on the native HIP kernels where the input is a 16-bit channels_last GPU "
+        "tensor; the gate is then computed in fp32 from the fp32 parameters; elsewhere (CPU, fp32, validation, "
+        "wider blocks) the modules fall back to their own forward",
+        "se", "convert_se", "{0} squeeze-excitation module(s) of {arch} converted"),
 )
 
 
