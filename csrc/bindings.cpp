@@ -37,6 +37,7 @@
 #include "kernels/loss.h"
 #include "kernels/optim.h"
 #include "kernels/pool.h"
+#include "kernels/mlp.h"
 #include "kernels/pwconv.h"
 #include "kernels/stem3x3.h"
 #include "kernels/stem.h"
@@ -1440,6 +1441,70 @@ int64_t pwconv_wgrad(const Tensor& x, const Tensor& dy, Tensor& ws, int64_t M, i
   return p.splits;
 }
 
+// ------------------------------------------------------- GELU MLP around the hidden tensor (mlp.hip)
+// z0 / dz [M][Hd], y / dy [M][Co] 16-bit, w2 [Co][Hd] (the backward data takes w2^T as [Hd][Co]) 16-bit, b1[Hd], b2[Co],
+// db1[Hd] fp32.  Hd % 8 == Co % 8 == 0, 8 <= Co <= 512, 8 <= Hd <= 2048; C is the width in front of the first Linear.
+bool mlp_fits(int64_t M, int64_t C, int64_t Hd, int64_t Co) { return pdt::mlp_fits(M, C, Hd, Co); }
+
+int mlp_geom(const char* op, const Tensor& hid, const Tensor& out, const Tensor* w, const Tensor& b1, int64_t M,
+             int64_t Hd, int64_t Co) {
+  TORCH_CHECK(pdt::mlp_fits(M, 8, Hd, Co), op, ": needs Hd % 8 == Co % 8 == 0, 8 <= Hd <= 2048, 8 <= Co <= 512 and "
+              "1 <= M <= 2^30, got M = ", M, ", Hd = ", Hd, ", Co = ", Co);
+  TORCH_CHECK(pf(b1, "b1") != nullptr && b1.numel() == Hd, op, ": b1 must hold Hd = ", Hd, " floats");
+  return pw_geom(op, hid, Hd, out, Co, w, M, Hd, Co);
+}
+
+// y[M][Co] = round16(gelu(z0[M][Hd] + b1) * w2[Co][Hd]^T + b2)
+void mlp_fc2_fwd(const Tensor& z0, const Tensor& b1, const Tensor& w2, const Tensor& b2, Tensor& y, int64_t M, int64_t Hd,
+                 int64_t Co) {
+  const int dt = mlp_geom("mlp_fc2_fwd", z0, y, &w2, b1, M, Hd, Co);
+  TORCH_CHECK(b2.numel() == Co, "mlp_fc2_fwd: b2 must hold Co = ", Co, " floats");
+  pdt::mlp_fc2_fwd_launch(dt, p16(z0, "z0"), pf(b1, "b1"), p16(w2, "w2"), pf(b2, "b2"), p16(y, "y"), M, (int)Hd, (int)Co,
+                          cur_stream());
+  launched("mlp_fc2_fwd");
+}
+
+// dz[M][Hd] = round16((dy[M][Co] * w2t[Hd][Co]^T) .* gelu'(z0 + b1)) and db1[Hd] = the column sums of the rounded dz;
+// max_blocks: persistent blocks aimed for (0 = the default).  Returns (partial rows, longest fp32 chain of a sum).
+std::vector<int64_t> mlp_fc2_dgrad(const Tensor& dy, const Tensor& w2t, const Tensor& z0, const Tensor& b1, Tensor& dz,
+                                   Tensor& db1, int64_t M, int64_t Hd, int64_t Co, int64_t max_blocks) {
+  const int dt = mlp_geom("mlp_fc2_dgrad", z0, dy, &w2t, b1, M, Hd, Co);
+  TORCH_CHECK(dt16(dz, "dz") == dt && dz.numel() == M * Hd && reinterpret_cast<uintptr_t>(dz.data_ptr()) % 16 == 0,
+              "mlp_fc2_dgrad: dz must be a 16-byte aligned [M][Hd] tensor of the operands' dtype");
+  TORCH_CHECK(db1.numel() == Hd && reinterpret_cast<uintptr_t>(pf(db1, "db1")) % 16 == 0,
+              "mlp_fc2_dgrad: db1 must hold Hd floats, 16-byte aligned");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks < (int64_t(1) << 30), "mlp_fc2_dgrad: bad max_blocks");
+  const pdt::MlpDgradPlan p = pdt::mlp_fc2_dgrad_launch(dt, p16(dy, "dy"), p16(w2t, "w2t"), p16(z0, "z0"), pf(b1, "b1"),
+                                                        p16(dz, "dz"), pf(db1, "db1"), M, (int)Hd, (int)Co,
+                                                        (int)max_blocks, cur_stream());
+  launched("mlp_fc2_dgrad");
+  return {p.row_blocks, p.chain};
+}
+
+// (splits, rows per split, 64-wide Hd tiles, 64-wide Co tiles, chain): the caller allocates ws = [splits][Co][Hd] fp32
+std::vector<int64_t> mlp_fc2_wgrad_plan(int64_t M, int64_t Hd, int64_t Co, int64_t target_blocks) {
+  TORCH_CHECK(pdt::mlp_fits(M, 8, Hd, Co) && target_blocks >= 1 && target_blocks < (int64_t(1) << 30),
+              "mlp_fc2_wgrad_plan: bad arguments");
+  const pdt::MlpWgradPlan p = pdt::mlp_fc2_wgrad_plan(M, (int)Hd, (int)Co, (int)target_blocks);
+  return {p.splits, p.rows_per_split, p.h_tiles, p.o_tiles, p.chain};
+}
+
+// partial slabs ws[splits][Co][Hd] (fp32) of dw2 = dy^T * round16(gelu(z0 + b1)) for the plan of `target_blocks`;
+// returns the split count to pass to wgrad_reduce (rows = Co, cols = Hd)
+int64_t mlp_fc2_wgrad(const Tensor& z0, const Tensor& b1, const Tensor& dy, Tensor& ws, int64_t M, int64_t Hd,
+                      int64_t Co, int64_t target_blocks) {
+  const int dt = mlp_geom("mlp_fc2_wgrad", z0, dy, nullptr, b1, M, Hd, Co);
+  TORCH_CHECK(target_blocks >= 1 && target_blocks < (int64_t(1) << 30), "mlp_fc2_wgrad: bad target_blocks");
+  const pdt::MlpWgradPlan p = pdt::mlp_fc2_wgrad_plan(M, (int)Hd, (int)Co, (int)target_blocks);
+  TORCH_CHECK(ws.numel() >= (int64_t)p.splits * Co * Hd, "mlp_fc2_wgrad: ws holds ", ws.numel(),
+              " floats, the plan needs ", (int64_t)p.splits * Co * Hd);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pf(ws, "ws")) % 16 == 0, "mlp_fc2_wgrad: ws must be 16-byte aligned");
+  pdt::mlp_fc2_wgrad_launch(dt, p16(z0, "z0"), pf(b1, "b1"), p16(dy, "dy"), pf(ws, "ws"), M, (int)Hd, (int)Co, p,
+                            cur_stream());
+  launched("mlp_fc2_wgrad");
+  return p.splits;
+}
+
 // ------------------------------------------------------- 3x3 / stride 2 / 3-channel first conv (stem3x3.hip)
 // x [N][H][W][3] fp32 NHWC (4-byte aligned), w [K][3][3][3] 16-bit KRSC, y / dy [N][P][Q][K] 16-bit, P = (H - 1) / 2 + 1,
 // Q = (W - 1) / 2 + 1; K % 8 == 0, 8 <= K <= 64.
@@ -2225,6 +2290,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pwconv_wgrad_plan", &pwconv_wgrad_plan, py::arg("M"), py::arg("C"), py::arg("K"), py::arg("target_blocks"));
   m.def("pwconv_wgrad", &pwconv_wgrad, py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("M"), py::arg("C"),
         py::arg("K"), py::arg("target_blocks"));
+  m.def("mlp_fits", &mlp_fits, py::arg("M"), py::arg("C"), py::arg("Hd"), py::arg("Co"));
+  m.def("mlp_fc2_fwd", &mlp_fc2_fwd, py::arg("z0"), py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("y"),
+        py::arg("M"), py::arg("Hd"), py::arg("Co"));
+  m.def("mlp_fc2_dgrad", &mlp_fc2_dgrad, py::arg("dy"), py::arg("w2t"), py::arg("z0"), py::arg("b1"), py::arg("dz"),
+        py::arg("db1"), py::arg("M"), py::arg("Hd"), py::arg("Co"), py::arg("max_blocks"));
+  m.def("mlp_fc2_wgrad_plan", &mlp_fc2_wgrad_plan, py::arg("M"), py::arg("Hd"), py::arg("Co"), py::arg("target_blocks"));
+  m.def("mlp_fc2_wgrad", &mlp_fc2_wgrad, py::arg("z0"), py::arg("b1"), py::arg("dy"), py::arg("ws"), py::arg("M"),
+        py::arg("Hd"), py::arg("Co"), py::arg("target_blocks"));
   m.def("stem3x3_fits", &stem3x3_fits, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("K"));
   m.def("stem3x3_fwd", &stem3x3_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("N"), py::arg("H"), py::arg("W"),
         py::arg("K"));

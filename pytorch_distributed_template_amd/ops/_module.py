@@ -1,5 +1,5 @@
-"""What the torch engine's drop-in modules (depthwise, depthwise7, stemconv, pointwise, layernorm, bnact, winattn, mha, se)
-share: the 16-bit dtypes, the autocast query, re-classing a module in place, the model walk, and the NHWC views of their
+"""What the torch engine's drop-in modules (depthwise, depthwise7, stemconv, pointwise, layernorm, bnact, winattn, mha, se,
+mlp) share: the 16-bit dtypes, the autocast query, re-classing a module in place, the model walk, and the NHWC views of their
 autograd functions.  Each module's eligibility test and its kernels' launch sequences stay with the module."""
 from __future__ import annotations
 

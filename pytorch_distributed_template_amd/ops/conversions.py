@@ -99,6 +99,16 @@ ATTENTION = (
         "tensor; the gate is then computed in fp32 from the fp32 parameters; elsewhere (CPU, fp32, validation, "
         "wider blocks) the modules fall back to their own forward",
         "se", "convert_se", "{0} squeeze-excitation module(s) of {arch} converted"),
+    Conversion(
+        "mlp",
+        "torch engine: run the channel MLPs of ConvNeXt, Swin and MaxViT blocks (a biased Linear, an exact-erf GELU, "
+        "optionally an inactive Dropout and a biased Linear in consecutive slots of an nn.Sequential; widths %% 8 == 0, "
+        "in and out within 8..512, hidden within 8..2048) on the native HIP kernels where the input is a dense GPU "
+        "tensor under 16-bit autocast: bias, GELU and its derivative are folded into the GEMMs around the hidden "
+        "tensor, and the first bias is added in fp32 after that GEMM's 16-bit rounding; wider MLPs (hidden 3072: "
+        "ConvNeXt's and Swin's last stage, every ViT block) and everything elsewhere (CPU, fp32, validation, active "
+        "dropout) stay on the stock ops",
+        "mlp", "convert_mlp", "{0} MLP(s) of {arch} converted"),
 )
 
 
